@@ -1,18 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/sec + achieved-HBM-bandwidth fraction on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one decoded token: one pass of the hot path (Forward, go/model.go:490-620
 restated as HIP kernels) plus the greedy argmax, chained on the device.
 
+A plain run measures the headline only: set up, W warm-up steps, ONE timed region of exactly K steps, the result line.
+--full adds everything else below (the timed region run REPEATS times with the median as the value, the per-launch
+profile and roofline, the CPU baseline and its greedy-id check, "secondary", "other_configs", the shard probe).
+--dump-outputs DIR writes what the timed path returned to its caller in its last step -- the greedy ids of the last
+nl_decode_greedy call, DIR/decode_ids.npy (float64) -- for output-for-output comparisons of two builds (same arguments,
+same inputs: the weights and the prompt are seeded).  --workload and --shard-of runs keep their per-launch profile.
+
   N = 1 : headline = BASELINE.json configs[1], nano (89M) Q8_0 single-stream greedy decode;
-          "secondary" = big (7.9B) Q4_0 on the one GPU (the 1-GPU point of configs[4]);
+          with --full: "secondary" = big (7.9B) Q4_0 on the one GPU (the 1-GPU point of configs[4]);
           "other_configs" = mini prefill, goldie prefill, goldie x 64 streams.
   N > 1 : headline = the SAME workload as N = 1 -- nano Q8_0 single-stream greedy decode -- as N independent
           replicas, one process per GPU, no data-path collective (the smallest tier does not shard: "scaling": "weak",
           value = tokens of all ranks / the slowest rank's time), so that the per-N values of one scaling run are
-          values of one metric.  "secondary" = BASELINE.json configs[4], big (7.9B) Q4_0 tensor-parallel over the N
+          values of one metric.  With --full, "secondary" = BASELINE.json configs[4], big (7.9B) Q4_0 tensor-parallel over the N
           GPUs (strong scaling: the two per-layer all-reduces are the push all-reduce over xGMI (nl_p2p_*), RCCL when
           that cannot be set up), with "reference_1gpu" = the same big model on rank 0's GPU alone, measured in the
           same run, and the first greedy ids compared against the tensor-parallel run.  A tensor-parallel transport
@@ -26,7 +33,7 @@ reports "ranks" = the number of distinct ranks that met in the rendezvous.
 
 Weights are a deterministic random-weight GGUF written on the box in the reference exporter's layout
 (nanollama_amd.synth); inputs are resident in HBM before the timed region.  The timed region -- exactly K steps
-between barrier + synchronize -- is run REPEATS times and the median is the value (min / max beside it).
+between barrier + synchronize -- is run once (--full: REPEATS times, the median is the value, min / max beside it).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -279,10 +286,12 @@ def persist_traffic_current():
     return False
 
 
-def run_workload(tier, wtype, rdv, steps, warmup, profile_pos, model, tp=True, comm=None, keep=None, shard_of=None, dropin=False):
+def run_workload(tier, wtype, rdv, steps, warmup, profile_pos, model, tp=True, comm=None, keep=None, shard_of=None, dropin=False,
+                 full=True):
     """Load the tier's random-weight GGUF, run `warmup` + REPEATS x `steps` chained greedy decode steps, profile the
-    launches.  tp=True: the ranks of rdv form one tensor-parallel engine (comm = "p2p" push all-reduce or "rccl");
-    tp=False: every rank is an independent replica (no data-path collective).  Timing = max over ranks."""
+    launches.  full=False: one timed region of `steps` steps and no profile (a plain bench.py run).  tp=True: the ranks
+    of rdv form one tensor-parallel engine (comm = "p2p" push all-reduce or "rccl"); tp=False: every rank is an
+    independent replica (no data-path collective).  Timing = max over ranks."""
     import numpy as np
     from nanollama_amd import gguf, synth
     rank, local_rank = rdv.rank, rdv.local_rank
@@ -320,10 +329,13 @@ def run_workload(tier, wtype, rdv, steps, warmup, profile_pos, model, tp=True, c
                 done += seg
             return ids
 
+        # one full segment before the warm-up (what a segment-long launch costs the first time stays out of the timed region);
+        # its ids are what the --full checks compare: against the CPU engine, the drop-in loops, the tensor-parallel run
         head_ids = dev.decode_greedy(first, pos0, min(SEGMENT, shape.seq_len - pos0))
         run_steps(warmup)
+        repeats = REPEATS if full else 1
         walls, evs, ids = [], [], []
-        for _ in range(REPEATS):
+        for _ in range(repeats):
             dev.synchronize()
             rdv.barrier()
             dev.timer_start()
@@ -334,98 +346,31 @@ def run_workload(tier, wtype, rdv, steps, warmup, profile_pos, model, tp=True, c
             evs.append(dev.timer_stop())
             rdv.barrier()
             walls.append(rdv.max_over_ranks(wall_ms))
-        order = sorted(range(REPEATS), key=lambda i: walls[i])
-        med = order[REPEATS // 2]
+        order = sorted(range(repeats), key=lambda i: walls[i])
+        med = order[repeats // 2]
         wall_ms = walls[med]
         ms_per_step = wall_ms / steps
-
-        # per-launch device time: every launch of the plan replayed 20x back to back between HIP events on the
-        # engine's stream (nl_profile_forward), at a mid-run position
-        ppos = min(profile_pos if profile_pos is not None else pos0 + (min(SEGMENT, steps) - 1) // 2, shape.seq_len - 1)
-        prof = dev.profile_forward(first, ppos, iters=20)
-        wo_in_block = bool(prof.get("attn_block", (0, 0))[1]) and not prof.get("wo_resid", (0, 0))[1]
-        kb = kernel_bytes(shape, wtype, ppos, tp=shard_of or world, wo_in_block=wo_in_block)
-        kernels = {}
-        for kind, (ms, calls) in prof.items():
-            if calls:
-                per = ms / calls
-                kernels[kind] = {"launches": calls, "us_per_launch": round(per * 1e3, 3),
-                                 "GBps": round(kb[kind] / (per * 1e-3) / 1e9, 1)}
-        traffic, traffic_file = measured_traffic(tier, wtype) if world == 1 else (None, None)
         if shard_of:
             world = 1        # (one GPU did the work: fractions below are against ONE device's peak, bytes are the shard's)
-        # dominant kernel = the kind with the largest TIME share of the step (launches x time per launch; ties broken by
-        # name); the kind that moves the most algorithmic bytes per step is reported beside it as roofline_by_bytes
-        cand = sorted(k for k in kernels if k not in ("argmax", "allreduce"))
-        dom = max(cand, key=lambda k: (prof[k][0], k))          # prof[k][0] = sum over the kind's launches of ms per launch
-        dom_bytes = max(cand, key=lambda k: (kb[k] * prof[k][1], k))
-        step_ms_profiled = sum(prof[k][0] for k in kernels)
-
-        def roof(kind):
-            return {"bound": "hbm", "kernel": kind, "achieved": kernels[kind]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(kernels[kind]["GBps"] / HBM_PEAK_GBS, 4), "traffic": (traffic or {}).get(kind),
-                    "traffic_source": traffic_file, "bytes_per_launch": int(kb[kind]),
-                    "us_per_launch": kernels[kind]["us_per_launch"], "launches_per_step": kernels[kind]["launches"],
-                    "time_share_of_step": round(prof[kind][0] / step_ms_profiled, 3), "profiled_at_pos": ppos}
         mean_pos = pos0 + (min(SEGMENT, steps) - 1) / 2.0
         step_bytes = (synth.weight_bytes_per_token(shape, wtype) + synth.kv_bytes_per_token(shape, int(mean_pos))) / (shard_of or 1)
         step_gbs = step_bytes / (ms_per_step * 1e-3) / 1e9
-        # The smallest tier's greedy chain is ONE persistent launch per segment (nl_persist.h): that launch IS the timed region's
-        # dominant kernel.  Its duration is measured live with HIP events on the engine's stream around single launches of the
-        # timed segment; achieved = algorithmic bytes of the segment's tokens (weights + f32 KV read per token, each
-        # byte counted once per token although the weights stay on chip for the whole launch) / that duration.
         pinfo = dev.persist_info() if world == 1 and not shard_of else {"ready": False}
-        persist_roof = None
-        if pinfo["ready"] and pos0 + min(SEGMENT, steps) <= pinfo["max_pos"]:
-            seg = min(SEGMENT, steps)
-            n0 = pinfo["launches"]
-            ts = []
-            for _ in range(7):
-                dev.synchronize()
-                dev.timer_start()
-                dev.decode_greedy(first, pos0, seg)
-                ts.append(dev.timer_stop())
-            ts.sort()
-            launch_ms = ts[len(ts) // 2]
-            assert dev.persist_info()["launches"] == n0 + 7, "the persistent launch was retired during the run: " + dev.last_error()
-            gbs = step_bytes * seg / (launch_ms * 1e-3) / 1e9
-            kernels["persistent_decode"] = {"launches": round(1.0 / seg, 5), "tokens_per_launch": seg, "us_per_launch": round(launch_ms * 1e3, 2),
-                                            "us_per_token": round(launch_ms * 1e3 / seg, 3), "GBps": round(gbs, 1)}
-            ptr = (traffic or {}).get("persistent_decode") or {}
-            ptraffic = ptr.get("bytes_per_launch") if ptr.get("tokens_per_launch") == seg and persist_traffic_current() else None
-            persist_roof = {"bound": "hbm", "kernel": "persistent_decode (pd_decode_kernel, nl_persist.h)", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
-                            "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": ptraffic, "traffic_source": traffic_file if ptraffic else None,
-                            "bytes_per_launch": int(step_bytes * seg), "us_per_launch": round(launch_ms * 1e3, 2), "tokens_per_launch": seg,
-                            "launches_per_step": round(1.0 / seg, 5), "time_share_of_step": round(min(1.0, launch_ms / seg / ms_per_step), 3),
-                            "note": "one launch decodes the whole segment with the weights resident on chip; bytes are the algorithmic bytes of its tokens"}
-            # What actually binds this launch is not HBM (its measured traffic is a fraction of the algorithmic bytes) but the chain of
-            # in-launch hand-offs a token walks through: per layer q|k|v -> heads (one in-XCD hop), then o, x', h and the layer's
-            # output each gathered by all 32 units of the XCD; per token seven cross-XCD hops and the chip-wide argmax exchange.
-            # Priced with the primitives tools/xcd_exchange_probe.hip measured (profiles/r05_xcd_exchange_probe.log): 0.25 us per
-            # in-XCD hop, 1.27 us per in-XCD all-gather of 576 values, 0.58 us per cross-XCD hop, 2.8 us chip-wide -- no compute.
-            n_layers = int(dev.config.num_layers)
-            chain_floor = n_layers * (4 * 1.27 + 0.25) + 7 * 0.58 + 2.8
-            persist_roof.update({
-                "binding": "latency of the in-launch hand-off chain (the weights never leave the chip), not HBM bandwidth",
-                "hbm_traffic_GBps_measured": (round(ptraffic / (launch_ms * 1e-3) / 1e9, 1) if ptraffic else None),
-                "chain_floor_us": round(chain_floor, 1),
-                "chain_floor_model": f"{n_layers} layers x (4 all-gathers x 1.27 + 1 hop x 0.25) + 7 cross-XCD hops x 0.58 + 2.8 (argmax exchange), us per token",
-                "us_per_token": round(launch_ms * 1e3 / seg, 2),
-                "chain_floor_frac": round(chain_floor / (launch_ms * 1e3 / seg), 3)})
-        p2p = dev.p2p_info() if (world > 1 or shard_of) else None
         res = {
             "tier": tier, "wtype": wtype, "path": path, "prompt": prompt,
             "tok_s": replicas * steps / (wall_ms / 1e3), "ms_per_step": ms_per_step, "device_ms_per_step": evs[med] / steps,
-            "ms_per_step_min": min(walls) / steps, "ms_per_step_max": max(walls) / steps,
-            "replicas": replicas, "tp": world, "p2p": p2p, "plan": dev.plan_info(),
+            "ms_per_step_min": min(walls) / steps, "ms_per_step_max": max(walls) / steps, "repeats": repeats,
+            "replicas": replicas, "tp": world, "plan": dev.plan_info(),
             "step_bytes": int(step_bytes), "hbm_frac_whole_step": step_gbs / (HBM_PEAK_GBS * max(world, 1)),
-            "kernels": kernels, "last_ids": ids[-4:], "head_ids": head_ids, "first_id": first, "prefill_logits": prefill_logits,
-            "dropin": (dropin_rates(dev, first, pos0, 64 if tier != "big" else 32, head_ids) if dropin and world == 1 and not shard_of else None),
-            "roofline": persist_roof or roof(dom), "roofline_by_bytes": roof(dom_bytes), "persist": pinfo,
-            "launch_plan_kernels_note": ("the per-kind entries beside persistent_decode are the launch plans this handle keeps for per-call Forward, "
-                                         "sampling and contexts beyond the persistent launch's position limit" if persist_roof else None),
-            "segment": min(SEGMENT, steps), "pos_first": pos0, "pos_last": pos0 + min(SEGMENT, steps) - 1,
+            "ids": ids, "last_ids": ids[-4:], "head_ids": head_ids, "first_id": first, "prefill_logits": prefill_logits,
+            "persist": pinfo, "segment": min(SEGMENT, steps), "pos_first": pos0, "pos_last": pos0 + min(SEGMENT, steps) - 1,
         }
+        if full:
+            res.update(launch_profile(dev, shape, tier, wtype, world, shard_of, first, pos0, steps, profile_pos, ms_per_step,
+                                      step_bytes, pinfo))
+            res["p2p"] = dev.p2p_info() if (res["tp"] > 1 or shard_of) else None
+            res["dropin"] = (dropin_rates(dev, first, pos0, 64 if tier != "big" else 32, head_ids)
+                             if dropin and res["tp"] == 1 and not shard_of else None)
     except BaseException:
         dev.close()      # (a failed attempt must not keep a 4 GB model and its receive area alive while a fallback loads another)
         raise
@@ -434,6 +379,81 @@ def run_workload(tier, wtype, rdv, steps, warmup, profile_pos, model, tp=True, c
     else:
         dev.close()
     return res
+
+
+def launch_profile(dev, shape, tier, wtype, world, shard_of, first, pos0, steps, profile_pos, ms_per_step, step_bytes, pinfo):
+    """--full: per-launch device times of the timed plan, the roofline of its dominant kernel, and the persistent launch
+    timed alone.  world = the ranks whose peak the fractions are against (1 for a shard timed alone)."""
+    # per-launch device time: every launch of the plan replayed 20x back to back between HIP events on the
+    # engine's stream (nl_profile_forward), at a mid-run position
+    ppos = min(profile_pos if profile_pos is not None else pos0 + (min(SEGMENT, steps) - 1) // 2, shape.seq_len - 1)
+    prof = dev.profile_forward(first, ppos, iters=20)
+    wo_in_block = bool(prof.get("attn_block", (0, 0))[1]) and not prof.get("wo_resid", (0, 0))[1]
+    kb = kernel_bytes(shape, wtype, ppos, tp=shard_of or world, wo_in_block=wo_in_block)
+    kernels = {}
+    for kind, (ms, calls) in prof.items():
+        if calls:
+            per = ms / calls
+            kernels[kind] = {"launches": calls, "us_per_launch": round(per * 1e3, 3),
+                             "GBps": round(kb[kind] / (per * 1e-3) / 1e9, 1)}
+    traffic, traffic_file = measured_traffic(tier, wtype) if world == 1 and not shard_of else (None, None)
+    # dominant kernel = the kind with the largest TIME share of the step (launches x time per launch; ties broken by
+    # name); the kind that moves the most algorithmic bytes per step is reported beside it as roofline_by_bytes
+    cand = sorted(k for k in kernels if k not in ("argmax", "allreduce"))
+    dom = max(cand, key=lambda k: (prof[k][0], k))          # prof[k][0] = sum over the kind's launches of ms per launch
+    dom_bytes = max(cand, key=lambda k: (kb[k] * prof[k][1], k))
+    step_ms_profiled = sum(prof[k][0] for k in kernels)
+
+    def roof(kind):
+        return {"bound": "hbm", "kernel": kind, "achieved": kernels[kind]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(kernels[kind]["GBps"] / HBM_PEAK_GBS, 4), "traffic": (traffic or {}).get(kind),
+                "traffic_source": traffic_file, "bytes_per_launch": int(kb[kind]),
+                "us_per_launch": kernels[kind]["us_per_launch"], "launches_per_step": kernels[kind]["launches"],
+                "time_share_of_step": round(prof[kind][0] / step_ms_profiled, 3), "profiled_at_pos": ppos}
+    # The smallest tier's greedy chain is ONE persistent launch per segment (nl_persist.h): that launch IS the timed region's
+    # dominant kernel.  Its duration is measured live with HIP events on the engine's stream around single launches of the
+    # timed segment; achieved = algorithmic bytes of the segment's tokens (SURVEY 8d: weights + f32 KV read per token, each
+    # byte counted once per token although the weights stay on chip for the whole launch) / that duration.
+    persist_roof = None
+    if pinfo["ready"] and pos0 + min(SEGMENT, steps) <= pinfo["max_pos"]:
+        seg = min(SEGMENT, steps)
+        n0 = dev.persist_info()["launches"]
+        ts = []
+        for _ in range(7):
+            dev.synchronize()
+            dev.timer_start()
+            dev.decode_greedy(first, pos0, seg)
+            ts.append(dev.timer_stop())
+        ts.sort()
+        launch_ms = ts[len(ts) // 2]
+        assert dev.persist_info()["launches"] == n0 + 7, "the persistent launch was retired during the run: " + dev.last_error()
+        gbs = step_bytes * seg / (launch_ms * 1e-3) / 1e9
+        kernels["persistent_decode"] = {"launches": round(1.0 / seg, 5), "tokens_per_launch": seg, "us_per_launch": round(launch_ms * 1e3, 2),
+                                        "us_per_token": round(launch_ms * 1e3 / seg, 3), "GBps": round(gbs, 1)}
+        ptr = (traffic or {}).get("persistent_decode") or {}
+        ptraffic = ptr.get("bytes_per_launch") if ptr.get("tokens_per_launch") == seg and persist_traffic_current() else None
+        persist_roof = {"bound": "hbm", "kernel": "persistent_decode (pd_decode_kernel, nl_persist.h)", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": ptraffic, "traffic_source": traffic_file if ptraffic else None,
+                        "bytes_per_launch": int(step_bytes * seg), "us_per_launch": round(launch_ms * 1e3, 2), "tokens_per_launch": seg,
+                        "launches_per_step": round(1.0 / seg, 5), "time_share_of_step": round(min(1.0, launch_ms / seg / ms_per_step), 3),
+                        "note": "one launch decodes the whole segment with the weights resident on chip; bytes are the algorithmic bytes of its tokens"}
+        # What actually binds this launch is not HBM (its measured traffic is a fraction of the algorithmic bytes) but the chain of
+        # in-launch hand-offs a token walks through: per layer q|k|v -> heads (one in-XCD hop), then o, x', h and the layer's
+        # output each gathered by all 32 units of the XCD; per token seven cross-XCD hops and the chip-wide argmax exchange.
+        # Priced with the primitives tools/xcd_exchange_probe.hip measured (profiles/r05_xcd_exchange_probe.log): 0.25 us per
+        # in-XCD hop, 1.27 us per in-XCD all-gather of 576 values, 0.58 us per cross-XCD hop, 2.8 us chip-wide -- no compute.
+        n_layers = int(dev.config.num_layers)
+        chain_floor = n_layers * (4 * 1.27 + 0.25) + 7 * 0.58 + 2.8
+        persist_roof.update({
+            "binding": "latency of the in-launch hand-off chain (the weights never leave the chip), not HBM bandwidth",
+            "hbm_traffic_GBps_measured": (round(ptraffic / (launch_ms * 1e-3) / 1e9, 1) if ptraffic else None),
+            "chain_floor_us": round(chain_floor, 1),
+            "chain_floor_model": f"{n_layers} layers x (4 all-gathers x 1.27 + 1 hop x 0.25) + 7 cross-XCD hops x 0.58 + 2.8 (argmax exchange), us per token",
+            "us_per_token": round(launch_ms * 1e3 / seg, 2),
+            "chain_floor_frac": round(chain_floor / (launch_ms * 1e3 / seg), 3)})
+    return {"kernels": kernels, "roofline": persist_roof or roof(dom), "roofline_by_bytes": roof(dom_bytes),
+            "launch_plan_kernels_note": ("the per-kind entries beside persistent_decode are the launch plans this handle keeps for per-call Forward, "
+                                         "sampling and contexts beyond the persistent launch's position limit" if persist_roof else None)}
 
 
 def prefill_x1(dev, toks, dt_hilo, gemm_flop):
@@ -670,16 +690,27 @@ def workload_text(shape, tier, wtype, r, steps):
 
 
 def summary(r, keys=("kernels",)):
-    out = {"value": round(r["tok_s"], 2), "unit": "tokens/s", "ms_per_step": round(r["ms_per_step"], 5),
-           "ms_per_step_min": round(r["ms_per_step_min"], 5), "ms_per_step_max": round(r["ms_per_step_max"], 5),
-           "hbm_frac_whole_step": round(r["hbm_frac_whole_step"], 4), "roofline": r["roofline"],
-           "roofline_by_bytes": r["roofline_by_bytes"]}
-    for k in keys:
-        out[k] = r[k]
+    out = {"value": round(r["tok_s"], 2), "unit": "tokens/s", "ms_per_step": round(r["ms_per_step"], 5)}
+    if r["repeats"] > 1:
+        out.update(ms_per_step_min=round(r["ms_per_step_min"], 5), ms_per_step_max=round(r["ms_per_step_max"], 5))
+    out["hbm_frac_whole_step"] = round(r["hbm_frac_whole_step"], 4)
+    if "roofline" in r:      # the per-launch profile (--full)
+        out.update(roofline=r["roofline"], roofline_by_bytes=r["roofline_by_bytes"])
+        for k in keys:
+            out[k] = r[k]
     if r.get("persist", {}).get("ready"):
         out["persistent_decode"] = r["persist"]      # nl_persist_info: the one-launch-per-chunk decode served the timed steps
-        out["launch_plan_kernels_note"] = r.get("launch_plan_kernels_note")
+        if "roofline" in r:
+            out["launch_plan_kernels_note"] = r.get("launch_plan_kernels_note")
     return out
+
+
+def dump_outputs(d, r):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the ids the last nl_decode_greedy
+    call of the timed region returned (its last entry is the last step's token) -- as float64, which holds them exactly."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "decode_ids.npy"), np.asarray(r["ids"], dtype=np.float64))
 
 
 def main():
@@ -697,7 +728,14 @@ def main():
     ap.add_argument("--no-shard-probe", action="store_true", help="N = 1: skip the tensor-parallel shard-only probe of big")
     ap.add_argument("--rccl-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--profile-pos", type=int, default=None, help="position of the per-launch profile (default: the mean timed position)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: REPEATS timed regions (median), the per-launch profile and roofline, the CPU "
+                         "baseline, the secondary tier, the side configs, the shard probe (a plain run times ONE region of --steps steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the ids the timed path returned in its last step to DIR/decode_ids.npy (float64)")
     args = ap.parse_args()
+    if args.dump_outputs and args.shard_of:
+        ap.error("--dump-outputs applies to the decode workloads, not to --shard-of (a shard's logits are not a model's)")
     n = args.gpus
     if n < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -730,8 +768,10 @@ def main():
             print(json.dumps({"n_gpus": n, "ranks": ranks_seen, "dryrun": True}))
         rdv.close()
         return
+    # --workload / --shard-of / the RCCL child are measurement tools: they always carry their per-launch profile
+    full = args.full or bool(args.workload or args.shard_of) or args.rccl_worker is not None
     common = {"unit": "tokens/s", "n_gpus": n, "ranks": ranks_seen, "steps": args.steps, "warmup": args.warmup,
-              "repeats": REPEATS, "higher_is_better": True, "vs_baseline": None, "dtype": "f32",
+              "repeats": REPEATS if full else 1, "higher_is_better": True, "vs_baseline": None, "dtype": "f32",
               "data": "synthetic (random-weight GGUF, reference exporter layout, nanollama_amd.synth)",
               "build": _lib.build_info()}
 
@@ -765,6 +805,8 @@ def main():
                    device_ms_per_step=round(r["device_ms_per_step"], 5), algorithmic_bytes_per_step=r["step_bytes"],
                    last_ids=r["last_ids"], **summary(r))
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, r)
             print(json.dumps(out))
         rdv.close()
         return
@@ -772,7 +814,10 @@ def main():
     if n == 1:
         tier, wtype = "nano", "q8_0"
         shape = synth.TIERS[tier]
-        r = run_workload(tier, wtype, rdv, args.steps, args.warmup, args.profile_pos, model, tp=False, dropin=not args.no_secondary)
+        r = run_workload(tier, wtype, rdv, args.steps, args.warmup, args.profile_pos, model, tp=False, dropin=not args.no_secondary,
+                         full=full)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r)
         out = dict(common, metric=f"decode tokens/sec, {tier} {wtype.upper()} single-stream greedy", scaling="weak",
                    config={"workload": workload_text(shape, tier, wtype, r, args.steps) + " per GPU", "parallelism": "single-gpu",
                            "weights": f"{wtype} blocks dequantised in-register, f32 activations and KV cache"},
@@ -781,7 +826,7 @@ def main():
         bad_ids = []
         if r.get("dropin"):
             out["dropin_forward_loop"] = r["dropin"]
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(r["path"], r["prompt"])
             out.update({"greedy_ids_vs_cpu": ids_check(out["cpu_baseline"], r["first_id"], r["head_ids"])})
             if not out["greedy_ids_vs_cpu"]["ids_match_cpu"]:
@@ -795,7 +840,7 @@ def main():
                     out["config0_nano_f16_cpu"] = f16
                 except Exception as exc:
                     out["config0_nano_f16_cpu"] = {"error": repr(exc)}
-        if not args.no_secondary:
+        if full and not args.no_secondary:
             # BASELINE.json's metric also names big Q4_0 @ 1 GPU: the 1-GPU point of the tensor-parallel curve
             try:
                 b = run_workload("big", "q4_0", rdv, 96, 16, args.profile_pos, model, dropin=True)
@@ -834,7 +879,9 @@ def main():
     # ---- N > 1: the headline workload as N independent replicas (weak scaling, no collective); the 7.9B tier tensor-parallel
     #      over the N GPUs (BASELINE.json configs[4]) as "secondary" ----
     tier, wtype = "nano", "q8_0"
-    r = run_workload(tier, wtype, rdv, args.steps, args.warmup, args.profile_pos, model, tp=False)
+    r = run_workload(tier, wtype, rdv, args.steps, args.warmup, args.profile_pos, model, tp=False, full=full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
     out = dict(common, metric=f"decode tokens/sec, {tier} {wtype.upper()} single-stream greedy", scaling="weak",
                config={"workload": workload_text(synth.TIERS[tier], tier, wtype, r, args.steps) + f" per GPU, {n} independent replicas",
                        "parallelism": f"replicas x{n} (one process per GPU, no data-path collective)",
@@ -845,7 +892,7 @@ def main():
     ref1 = None
     tp_res, transport, notes = None, None, []
     watchdog = None
-    if not args.no_secondary:
+    if full and not args.no_secondary:
         # The tensor-parallel wire has never run across devices on this repository's test pool: whatever it
         # does on the real node -- every poll in it is bounded, RCCL runs in guarded children -- it must not take the measured
         # headline with it.  Past the deadline every rank leaves; rank 0 prints the line it has.
@@ -909,7 +956,7 @@ def main():
     if watchdog is not None:
         watchdog.cancel()
     if rank == 0:
-        if not args.no_secondary:
+        if full and not args.no_secondary:
             sec = {"metric": f"decode tokens/sec, big Q4_0 single-stream greedy, tensor-parallel over {n} GPUs", "scaling": "strong"}
             if tp_res is None:
                 sec.update(value=None, error="no tensor-parallel transport worked", attempts=notes)

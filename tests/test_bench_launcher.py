@@ -50,3 +50,23 @@ def test_under_a_launcher_the_ranks_come_from_the_environment():
     outs = [p.communicate(timeout=120) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
     assert json.loads(outs[0][0].strip().splitlines()[-1])["ranks"] == 2
+
+
+def test_dump_outputs_writes_the_ids_exactly_as_float64(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = [5, 17, 95999, 2 ** 31 - 1]
+    bench.dump_outputs(str(tmp_path / "out"), {"ids": ids})
+    got = np.load(tmp_path / "out" / "decode_ids.npy")
+    assert got.dtype == np.float64 and got.tolist() == ids
+
+
+def test_a_plain_line_carries_the_headline_without_the_profile():
+    sys.path.insert(0, ROOT)
+    import bench
+    r = {"tok_s": 8000.0, "ms_per_step": 0.125, "ms_per_step_min": 0.125, "ms_per_step_max": 0.125, "repeats": 1,
+         "hbm_frac_whole_step": 0.08, "persist": {"ready": False}}
+    s = bench.summary(r)
+    assert (s["value"], s["unit"], s["ms_per_step"]) == (8000.0, "tokens/s", 0.125)
+    assert not {"roofline", "roofline_by_bytes", "kernels", "ms_per_step_min"} & set(s)

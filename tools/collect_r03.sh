@@ -3,8 +3,8 @@
 ulimit -c 0; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r03; rm -rf $O; mkdir -p $O
 (timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -8) > $O/pytest_gpu.log
-(timeout 900 python bench.py 2>$O/bench_n1.err | tail -1) > $O/r03_bench_n1.json.log
-(timeout 900 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1) > $O/r03_bench_n1_steps20.json.log
+(timeout 900 python bench.py --full 2>$O/bench_n1.err | tail -1) > $O/r03_bench_n1.json.log
+(timeout 900 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | tail -1) > $O/r03_bench_n1_steps20.json.log
 # kernel stats (eager launches: rocprofv3 cannot trace graph replays on this image)
 bash scripts_gpu_run.sh prof > $O/prof_head.txt 2>&1
 cp gpurun_out/prof/nano_kernel_stats.csv $O/r03_nano_q8_0_kernel_stats.csv 2>/dev/null; cp gpurun_out/prof/big_kernel_stats.csv $O/r03_big_q4_0_kernel_stats.csv 2>/dev/null

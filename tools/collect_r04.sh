@@ -63,8 +63,8 @@ d=json.loads(sys.stdin.read())
 print('$wl', d['value'],'tok/s', d['ms_per_step'],'ms', {k:v['us_per_launch'] for k,v in d['kernels'].items()})"
   done; done ;;
 bench)
-  (timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench_steps20.err | tail -1) > $O/r04_bench_n1_steps20.json.log
-  (timeout 900 python bench.py 2>$O/bench_n1.err | tail -1) > $O/r04_bench_n1.json.log
+  (timeout 900 python bench.py --steps 20 --warmup 5 --full 2>$O/bench_steps20.err | tail -1) > $O/r04_bench_n1_steps20.json.log
+  (timeout 900 python bench.py --full 2>$O/bench_n1.err | tail -1) > $O/r04_bench_n1.json.log
   cut -c1-600 $O/r04_bench_n1_steps20.json.log ;;
 stats)
   bash scripts_gpu_run.sh prof > $O/prof_head.txt 2>&1

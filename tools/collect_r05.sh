@@ -18,7 +18,7 @@ xcd)
 tests)
   (timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -25) > $O/pytest_gpu.log; cat $O/pytest_gpu.log ;;
 bench)
-  (timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench_steps20.err | tail -1) > $O/r05_bench_n1_steps20.json.log
+  (timeout 900 python bench.py --steps 20 --warmup 5 --full 2>$O/bench_steps20.err | tail -1) > $O/r05_bench_n1_steps20.json.log
   cut -c1-700 $O/r05_bench_n1_steps20.json.log ;;
 pfab)
   # NL_PREFETCH A/B on the big tier (nl_tp.h PfTiles): bits 1 attention -> ffn round 0, 2 ffn -> next projection, 4 ffn round-ahead
@@ -54,7 +54,8 @@ newtests_unused)
 prof)
   # rocprofv3 per-kernel stats of the driver's own bench command (nano: the persistent launch) and of big; HBM traffic counters, one PMC pass per counter
   rm -rf gpurun_out/prof5; mkdir -p gpurun_out/prof5
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof5 -o nano -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > gpurun_out/prof5/nano.log 2>&1 < /dev/null
+  P=$(dirname $O)/prof5
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o nano -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $P/nano.log 2>&1 < /dev/null
   NL_NO_GRAPH=1 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof5 -o big -- python3 bench.py --workload big:q4_0 --steps 64 --warmup 8 --no-cpu-baseline > gpurun_out/prof5/big.log 2>&1 < /dev/null
   for t in nano big; do f=$(ls gpurun_out/prof5/${t}_kernel_stats.csv gpurun_out/prof5/*/${t}_kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp "$f" $O/r05_${t}_kernel_stats.csv && head -8 "$f" | cut -c1-170; done
   grep '^{' gpurun_out/prof5/nano.log | tail -1 > $O/r05_bench_n1_steps20_under_rocprof.json.log
@@ -70,7 +71,7 @@ PY
   cat $O/r05_nano_pd_decode_dispatch_durations.csv | tr '\n' ' '; echo
   for ctr in FETCH_SIZE WRITE_SIZE; do
     out=gpurun_out/pmc5_$ctr; rm -rf $out; mkdir -p $out
-    timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out -o p -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $out/log.txt 2>&1 < /dev/null
+    timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out -o p -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $out/log.txt 2>&1 < /dev/null
     f=$(ls $out/*counter_collection.csv $out/*/*counter_collection.csv 2>/dev/null | head -1)
     if [ -n "$f" ]; then python3 - "$f" "$ctr" > $O/r05_nano_q8_0_pmc_${ctr}.csv <<'PY'
 import csv, sys, collections

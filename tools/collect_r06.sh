@@ -26,13 +26,14 @@ PY
 for target in "$@"; do
 case $target in
 bench)
-  (timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench_steps20.err | tail -1) > $O/r06_bench_n1_steps20.json.log
+  (timeout 900 python bench.py --steps 20 --warmup 5 --full 2>$O/bench_steps20.err | tail -1) > $O/r06_bench_n1_steps20.json.log
   cut -c1-600 $O/r06_bench_n1_steps20.json.log; echo
-  (timeout 900 python bench.py 2>$O/bench_default.err | tail -1) > $O/r06_bench_n1.json.log
+  (timeout 900 python bench.py --full 2>$O/bench_default.err | tail -1) > $O/r06_bench_n1.json.log
   cut -c1-600 $O/r06_bench_n1.json.log; echo ;;
 prof)
   rm -rf gpurun_out/prof6; mkdir -p gpurun_out/prof6
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof6 -o nano -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > gpurun_out/prof6/nano.log 2>&1 < /dev/null
+  P=$(dirname $O)/prof6
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o nano -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $P/nano.log 2>&1 < /dev/null
   NL_NO_GRAPH=1 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof6 -o big -- python3 bench.py --workload big:q4_0 --steps 64 --warmup 8 --no-cpu-baseline > gpurun_out/prof6/big.log 2>&1 < /dev/null
   for t in nano big; do f=$(ls gpurun_out/prof6/${t}_kernel_stats.csv gpurun_out/prof6/*/${t}_kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp "$f" $O/r06_${t}_kernel_stats.csv && head -6 "$f" | cut -c1-170; done
   grep '^{' gpurun_out/prof6/nano.log | tail -1 > $O/r06_bench_n1_steps20_under_rocprof.json.log
@@ -47,7 +48,7 @@ PY
   tr '\n' ' ' < $O/r06_nano_pd_decode_dispatch_durations.csv; echo
   for ctr in FETCH_SIZE WRITE_SIZE; do
     out=gpurun_out/pmc6_$ctr; rm -rf $out; mkdir -p $out
-    timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out -o p -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $out/log.txt 2>&1 < /dev/null
+    timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out -o p -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $out/log.txt 2>&1 < /dev/null
     f=$(ls $out/*counter_collection.csv $out/*/*counter_collection.csv 2>/dev/null | head -1)
     if [ -n "$f" ]; then
       pmc_by_kernel "$f" $ctr > $O/r06_nano_q8_0_pmc_${ctr}.csv

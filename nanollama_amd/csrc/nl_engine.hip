@@ -32,6 +32,7 @@
 #include <condition_variable>
 #include <chrono>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -41,6 +42,123 @@ namespace { void samp_free(nl::SampScratch &s); }
 using namespace nl;
 
 namespace {
+
+// ---- environment knobs (development, tests, tools) ----------------------------------------------------------------------------
+// Every NL_* variable the library reads is read here and nowhere else, at one of three points.  process: once, at the first use of
+// any (process_knobs()).  handle: in nl_create (nl_engine::knobs; nl_op_matmul's temporary engine: per call).  step: once per call
+// of nl_prefill / nl_forward_batch / nl_op_matmul_batch (StepKnobs): tests and bench.py flip them on a live handle, and a cached
+// decode-batch step graph is keyed on all of them.  Values parse as atoi does (junk is 0); "set": present, whatever the value.
+//
+//   knob                          default     read     switches
+//   NL_WAVES                      2048        process  wavefronts in flight a GEMV's geometry aims for (choose_geometry)
+//   NL_GRAPH_STEPS                16          process  plan steps per graph of chained greedy decode
+//   NL_NO_ARGMAX_EMBED            unset       process  set: chained decode keeps the embed launch of every step
+//   NL_ATTN_F32, NL_NO_ATTN_TILE  unset       process  set: prompt attention on the f32-MFMA tile kernel / on attn_kernel per token
+//   NL_NO_ATTN_FIN                unset       process  set: one-split attention of a multi-token step keeps the merge launch
+//   NL_BATCH_MIN                  3           process  fewest tokens that take the multi-token step (prompts, decode batches)
+//   NL_FUSED_SWIGLU_MIN_WG,       128, 128    process  workgroups from which gate || up (SwiGLU) / Q|K|V (RoPE + KV store) run
+//     NL_FUSED_ROPE_MIN_WG                             with their fused GEMM epilogue (tests: 1)
+//   NL_QG_RSTAGE                  1           process  0: one-tile GEMMs stage their fragments by LDS-DMA, not through registers
+//   NL_QG_FORCE_WAVES             0           process  4 or 8: wavefronts per workgroup of the multi-token GEMM
+//   NL_QG_DEC_GEOM                0           process  82: decode-batch GEMM workgroups of 8 wavefronts x 2 tiles
+//   NL_KS_CAP, NL_QG_MIN_WG       16, 128     process  split-K of the multi-token GEMM: largest split; workgroups it splits to
+//   NL_QG_MAX_CHUNKS,             6, 1024     process  ... and on while a decode-batch workgroup walks more 128-column chunks,
+//     NL_QG_MAX_WG                                     up to this many workgroups
+//   NL_NO_GRAPH                   unset       handle   set: no hipGraphs, the host queues every launch
+//   NL_FORCE_TP_PLAN              unset       handle   set: the all-reduce / all-gather seams even with one rank
+//   NL_QUIET                      unset       handle   set: no warnings on stderr
+//   NL_TW, NL_KW                  0, 0        handle   > 0: tiles per workgroup / wavefronts per tile of every GEMV
+//   NL_SUB_BATCHES                1           handle   decode batches as up to 4 concurrent sub-batches (clamped to 1 .. 4)
+//   NL_NO_BATCH_PATH              unset       handle   set: prompts and decode batches stay on single-token steps
+//   NL_NO_CALL_BOX,               unset       handle   set: per-call Forward copies its control words and synchronises /
+//     NL_NO_HOST_LOGITS                                reads the logits back by DMA
+//   NL_NO_SAMPLE_EMBED            unset       handle   set: the sampled-decode graph keeps the plan's embed and argmax launches
+//   NL_FUSED_ATTN                 -1          handle   0: the five-launch plan only; 2: forces mode 2 (projection + attention)
+//   NL_FUSED_FFN                  1           handle   0: mode 1 keeps gate / up and down as two launches
+//   NL_FUSED_MAX_POS              by mode     handle   positions below which the fused plan serves a step
+//   NL_FUSED_SPIN_LIMIT           400000      handle   polls before a cluster exchange gives up (0 forces the fallback)
+//   NL_ATTN_WO                    1           handle   0: wide tiers on one GPU keep mode 2 (WO as its own launch)
+//   NL_ATTN_HELPERS               1           handle   0: mode 4 without the helper blocks of long contexts
+//   NL_WIDE_FFN                   1           handle   0: never wide_ffn_kernel; 2: also when its grid does not fill the chip
+//   NL_MFMA_DOT                   1           handle   0: wide launches' dot products on the vector pipe; 2: attention's too
+//   NL_PREFETCH                   1           handle   L2 warm-up bits (nl_tp.h PfTiles): 1 = the attention launch warms round 0 of
+//                                                      the feed-forward launch; 2 / 4 / 8 / 16 left off (profiles/r05_prefetch_ab.log)
+//   NL_TP_FUSED                   1           handle   0: a tensor-parallel rank keeps the projection + attention plan
+//   NL_TP_PAIR                    by shape    handle   1 / 0: feed-forward producers take a gate + up tile pair / one tile
+//   NL_TP_CT                      by shape    handle   W_down tiles per consumer block of the two-launch layer
+//   NL_TP_WIDE                    0           handle   non-zero: a rank prefers wide_ffn_kernel wherever it is eligible
+//   NL_PERSIST                    1           handle   0: greedy chains stay on the launch plans
+//   NL_PERSIST_MAX_POS            PD_MAX_POS  handle   position limit of the persistent decode (clamped to 0 .. PD_MAX_POS)
+//   NL_PERSIST_SPIN_LIMIT         2000000     handle   polls before a hand-off of the persistent decode gives up (0: at once)
+//   NL_PERSIST_SESSION            1           handle   0: per-call Forward is one launch per step, no resident session
+//   NL_PERSIST_IDLE_US            2000        handle   microseconds a resident session waits for the next token (1 .. 2e6)
+//   NL_PERSIST_FAKE_CENSUS_MISS   0           handle   test: the first n persistent launches count as placement misses
+//   NL_P2P_CACHED                 unset       handle   set: cached push all-reduce receive area (ranks on ONE device only)
+//   NL_P2P_TIMEOUT_MS             10000       handle   push all-reduce: how long a poll waits for a peer
+//   NL_PREFILL_PRECISION          hi + lo     step     fp16x1: long-prompt GEMMs and prompt attention multiply the fp16 hi half
+//                                                      only (11-bit activations, half / a third of the matrix work; hi + lo
+//                                                      keeps float32-grade results); fp16x1-gemm / fp16x1-attn: one of the two
+//   NL_QG2_MIN_TOKENS             128         step     tokens from which Q4_0 GEMMs run on qgemm2_kernel (huge: never)
+//   NL_FOLD_NORM                  1           step     0: a Q4_0 prompt keeps its bnorm launches
+//   NL_ROPE_IN_ATTN               1           step     0: a decode batch keeps its brope_kv launch
+//   NL_KV16_MIN_TOKENS            256         step     prompt tokens from which the attention converts K / V once per layer
+//   NL_ATT_RUN                    0           step     > 0: fixed run length of the prompt attention workgroups
+//   NL_DGEMM                      1           step     0: multi-token steps keep the split-K / long-run GEMMs
+//   NL_DGEMM_MAX_TOKENS           by shape    step     longest step dgemm_kernel takes (dgemm_step_ok)
+//   NL_DGEMM_HEAD                 1           step     0: a decode batch's LM head stays bnorm + split-K + argmax
+std::optional<int> knob_opt(const char *name) { const char *v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; }
+int knob_int(const char *name, int dflt) { return knob_opt(name).value_or(dflt); }
+bool knob_off(const char *name) { return knob_opt(name) == 0; }     // set and 0
+bool knob_set(const char *name) { return getenv(name) != nullptr; }
+long long knob_ll(const char *name, long long dflt) { const char *v = getenv(name); return v ? atoll(v) : dflt; }
+
+// (constructing one of these reads the environment)
+struct ProcessKnobs {
+    int waves = knob_int("NL_WAVES", 2048), graph_steps = knob_int("NL_GRAPH_STEPS", 16), batch_min = knob_int("NL_BATCH_MIN", 3);
+    bool argmax_embed = !knob_set("NL_NO_ARGMAX_EMBED"), qg_rstage = !knob_off("NL_QG_RSTAGE");
+    bool attn_f32 = knob_set("NL_ATTN_F32"), no_attn_tile = knob_set("NL_NO_ATTN_TILE"), no_attn_fin = knob_set("NL_NO_ATTN_FIN");
+    int fused_swiglu_min_wg = knob_int("NL_FUSED_SWIGLU_MIN_WG", 128), fused_rope_min_wg = knob_int("NL_FUSED_ROPE_MIN_WG", 128);
+    int qg_force_waves = knob_int("NL_QG_FORCE_WAVES", 0), qg_dec_geom = knob_int("NL_QG_DEC_GEOM", 0), ks_cap = knob_int("NL_KS_CAP", 16);
+    int qg_min_wg = knob_int("NL_QG_MIN_WG", 128), qg_max_chunks = knob_int("NL_QG_MAX_CHUNKS", 6), qg_max_wg = knob_int("NL_QG_MAX_WG", 1024);
+};
+// (one reading for the whole process: batched_step's attention workgroup list and the launchers must agree on the kernel)
+const ProcessKnobs &process_knobs() { static const ProcessKnobs k; return k; }
+
+struct HandleKnobs {
+    bool no_graph = knob_set("NL_NO_GRAPH"), force_tp_plan = knob_set("NL_FORCE_TP_PLAN"), quiet = knob_set("NL_QUIET");
+    int tw = knob_int("NL_TW", 0), kw = knob_int("NL_KW", 0), sub_batches = std::max(1, std::min(4, knob_int("NL_SUB_BATCHES", 1)));
+    bool batch_path = !knob_set("NL_NO_BATCH_PATH"), call_box = !knob_set("NL_NO_CALL_BOX"), host_logits = !knob_set("NL_NO_HOST_LOGITS"),
+         sample_embed = !knob_set("NL_NO_SAMPLE_EMBED");
+    int fused_attn = knob_int("NL_FUSED_ATTN", -1), fused_spin_limit = knob_int("NL_FUSED_SPIN_LIMIT", 400000);
+    bool fused_ffn = !knob_off("NL_FUSED_FFN"), attn_wo = !knob_off("NL_ATTN_WO"), attn_helpers = !knob_off("NL_ATTN_HELPERS");
+    std::optional<int> fused_max_pos = knob_opt("NL_FUSED_MAX_POS");
+    int wide_ffn = knob_int("NL_WIDE_FFN", 1), mfma_dot = knob_int("NL_MFMA_DOT", 1), prefetch = knob_int("NL_PREFETCH", 1);
+    bool tp_fused = !knob_off("NL_TP_FUSED"), tp_wide = knob_int("NL_TP_WIDE", 0) != 0;
+    std::optional<int> tp_pair = knob_opt("NL_TP_PAIR"), tp_ct = knob_opt("NL_TP_CT");
+    bool persist = !knob_off("NL_PERSIST"), persist_session = knob_int("NL_PERSIST_SESSION", 1) != 0, p2p_cached = knob_set("NL_P2P_CACHED");
+    int persist_max_pos = std::max(0, std::min(PD_MAX_POS, knob_int("NL_PERSIST_MAX_POS", PD_MAX_POS))), p2p_timeout_ms = knob_int("NL_P2P_TIMEOUT_MS", 10000);
+    int persist_spin_limit = knob_int("NL_PERSIST_SPIN_LIMIT", 2000000), persist_fake_misses = knob_int("NL_PERSIST_FAKE_CENSUS_MISS", 0);
+    long long persist_idle_ticks = std::max(1LL, std::min(2000000LL, knob_ll("NL_PERSIST_IDLE_US", 2000))) * 100;   // 100 MHz clock
+};
+
+enum class Precision { hi_lo, fp16x1, fp16x1_gemm, fp16x1_attn };     // NL_PREFILL_PRECISION: unset, fp16x1, fp16x1-gemm, fp16x1-attn
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-extensions"
+struct StepKnobs {
+    Precision prefill = [] {
+        const char *v = getenv("NL_PREFILL_PRECISION");
+        const std::string s = v ? v : "";
+        return s == "fp16x1" ? Precision::fp16x1 : s == "fp16x1-gemm" ? Precision::fp16x1_gemm : s == "fp16x1-attn" ? Precision::fp16x1_attn : Precision::hi_lo;
+    }();
+    int qg2_min_tokens = knob_int("NL_QG2_MIN_TOKENS", 128), kv16_min_tokens = knob_int("NL_KV16_MIN_TOKENS", 256), att_run = knob_int("NL_ATT_RUN", 0);
+    bool fold_norm = !knob_off("NL_FOLD_NORM"), rope_in_attn = !knob_off("NL_ROPE_IN_ATTN"), dgemm = !knob_off("NL_DGEMM"),
+         dgemm_head = !knob_off("NL_DGEMM_HEAD");
+    std::optional<int> dgemm_max_tokens = knob_opt("NL_DGEMM_MAX_TOKENS");
+    bool operator==(const StepKnobs &) const = default;
+    int x1_gemm() const { return prefill == Precision::fp16x1 || prefill == Precision::fp16x1_gemm; }
+    int x1_attn() const { return prefill == Precision::fp16x1 || prefill == Precision::fp16x1_attn; }
+};
+#pragma clang diagnostic pop
 
 thread_local std::string g_create_error;
 // Allocation / graph-capture sections of different rank engines of ONE process (nl_create_group: a host thread per rank) must not
@@ -221,19 +339,18 @@ struct nl_engine {
     // Concurrent sub-batches of a decode batch (nl_forward_batch): the streams of a batch are independent (go/serve.go:106-108
     // serialises them only because it has one CPU engine), so the batch is cut into groups that step on their own HIP stream
     // with their own step buffers -- one dependent chain's launch heads and memory round trips overlap another's work.
-    // Each group's step is a hipGraph cached by (tokens, position splits): twice the launches would otherwise bind on the host.
+    // Each group's step is a hipGraph cached by (tokens, position splits, step knobs): twice the launches would otherwise bind on the host.
+    struct StepGraph { int m; int nsplit; StepKnobs knobs; hipGraph_t graph; hipGraphExec_t exec; };
     struct SubBatch {
         Batch bt;
         hipStream_t st = nullptr;
         hipEvent_t done = nullptr;
-        struct G { int n, nsplit; hipGraph_t graph; hipGraphExec_t exec; };
-        std::vector<G> graphs;
+        std::vector<StepGraph> graphs;
     } sub[4];
     int dg_state = 0;             // dgemm_kernel's weight copies: 0 not looked at yet, 1 built, -1 the model does not qualify
     bool dg_head = false;         // ... and the LM head has one too (decode batches: dgemm_kernel with the argmax candidates in its epilogue)
-    std::vector<SubBatch::G> bt_graphs;   // step graphs of the whole-batch decode step (bt), same key
+    std::vector<StepGraph> bt_graphs;   // step graphs of the whole-batch decode step (bt), same key
     hipEvent_t sub_fork = nullptr;
-    int sub_batches = 1;          // NL_SUB_BATCHES: groups a decode batch is cut into (1 = the whole batch as one step: measured fastest, profiles/r04_subbatch_groups.log)
 
     // on-device sampling (nl_sample_decode): scratch for one vocabulary, allocated on first use
     SampScratch sp;
@@ -257,10 +374,6 @@ struct nl_engine {
                                   // 3: a tensor-parallel rank's layer as two launches (nl_tp.h); 4: one GPU, wide tier: mode 3's
                                   // attention half with a direct seam (projection + attention + WO), then the two GEMVs
     bool mf_attn = false, mf_ffn = false;   // the attention / feed-forward launch of modes 3 / 4 multiplies on the matrix pipe (NL_MFMA_DOT=0: off)
-    int prefetch = 1;             // NL_PREFETCH bits (nl_tp.h PfTiles): 1 = the attention launch warms round 0 of the feed-forward launch (kept:
-                                  // big 670 -> 698 tok/s); measured and left off (profiles/r05_prefetch_ab.log): 2 = the feed-forward launch warms
-                                  // the next layer's projection tiles (+0.8 %), 4 = a feed-forward round warms the round after the next (-5 %: two
-                                  // rounds and the touched one exceed the L2), 8 = bit 1's touches issued right after the block's own projection
     bool wide_ffn = false;        // modes 3 / 4: the feed-forward half is wide_ffn_kernel (nl_tp.h): always in mode 4 when eligible, in
                                   // mode 3 when the rank's shard is too large for tp_ffn_kernel's one-tile producers (tp 2 of the 7.9B tier)
     int wide_nf = 1, wide_ngc = 1;
@@ -285,7 +398,6 @@ struct nl_engine {
     unsigned *tick = nullptr;     // {forward counter, status} device words of the fused block
     long long *dbg_block = nullptr;
     unsigned *h_status = nullptr; // pinned, device-visible: non-zero after an in-kernel exchange gave up
-    int spin_limit = 400000;      // polls before a cluster exchange gives up (NL_FUSED_SPIN_LIMIT)
     int num_cus = 256;            // compute units of the device: a fused launch must fit on them all at once
     bool fused_retired = false;   // an exchange timed out once: the handle stays on the general plan
     int graph_steps = 1;
@@ -333,16 +445,14 @@ struct nl_engine {
         float *norms = nullptr;      // [L][2][D] + [D]: attn_norm | ffn_norm of every layer, output_norm (one pointer for the kernel)
         unsigned tag_base = 0;
         int max_pos = PD_MAX_POS;
-        int spin_limit = 2000000;
         long long *dbg = nullptr;
         long long launches = 0, tokens = 0;
         // resident session (per-call Forward): the launch stays on the chip between nl_forward calls and takes every next
         // token from a pinned mailbox word; see PdParams::session
-        bool session_on = true;      // NL_PERSIST_SESSION=0: one launch of one step per call instead
+        bool session_on = true;      // (NL_PERSIST_SESSION=0: one launch of one step per call instead)
         bool live = false;           // a session launch is (or may still be) resident on e->stream
         bool s_logits = false;       // ... whose LM-head units store every step's logits into h_logits
         int s_stream = 0, s_next_pos = 0, s_step = 0, s_nsteps = 0;
-        long long idle_ticks = 200000;   // 2 ms of the 100 MHz clock (NL_PERSIST_IDLE_US)
         pd_u64 *h_mail = nullptr, *d_mail = nullptr;   // pinned: [0] mailbox, [8] done word (own cache lines); device view
         pd_u64 *gtok = nullptr;
         unsigned launch_no = 0;
@@ -353,8 +463,7 @@ struct nl_engine {
     // with plain peer pointers.  Every entry point called on the leader runs the same entry point on every member, each
     // on its own host thread (a rank's step cannot finish before its peers have launched theirs).
     struct GroupCtl *grp = nullptr;
-    int tw_override = 0, kw_override = 0;
-    bool force_tp_plan = false;  // NL_FORCE_TP_PLAN: use the all-reduce / all-gather seams even with one rank
+    HandleKnobs knobs;            // read when the engine is constructed (nl_create)
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -463,14 +572,14 @@ void choose_geometry(const nl_engine *e, const PackedMat &m, int &tw, int &kw, i
     // wavefronts in flight (8 per CU); small matrices go all the way to one group per wavefront,
     // which is what minimises the in-launch latency of small models.
     const int ngroups = (m.npairs + KL - 1) / KL;
-    static const int target = getenv("NL_WAVES") ? atoi(getenv("NL_WAVES")) : 2048;   // developer knob (tools/)
+    const int target = process_knobs().waves;
     kw = (target + m.ntiles - 1) / std::max(1, m.ntiles);
     const int cap = 8 / mats;  // workgroups are capped at 8 wavefronts (256 VGPRs each)
     kw = (kw + mats - 1) / mats;
     kw = std::max(1, std::min(kw, std::min(ngroups, cap)));
     tw = std::max(1, 4 / (kw * mats));
-    if (e->kw_override > 0) kw = std::min(e->kw_override, cap);
-    if (e->tw_override > 0) tw = e->tw_override;
+    if (e->knobs.kw > 0) kw = std::min(e->knobs.kw, cap);
+    if (e->knobs.tw > 0) tw = e->knobs.tw;
     if (tw * kw * mats > 8) tw = std::max(1, 8 / (kw * mats));
     if (tw > m.ntiles) tw = m.ntiles;
 }
@@ -562,22 +671,10 @@ hipError_t launch_attn(int hd, int gqa, AttnParams P, dim3 grid, hipStream_t st)
     return hipErrorInvalidValue;
 }
 
-// developer knobs of the prompt attention, read ONCE per process and in one place: the workgroup list of batched_step
-// and the launchers below must agree on which kernel runs (a list built for attn_tile16_kernel is not a grid of the f32
-// tile kernel)
-struct AttnKnobs { bool f32_tile, no_tile, no_fin; };
-static const AttnKnobs &attn_knobs() {
-    static const AttnKnobs k{getenv("NL_ATTN_F32") != nullptr,       // the f32-MFMA tile kernel
-                             getenv("NL_NO_ATTN_TILE") != nullptr,   // no tile kernel at all: attn_kernel per token
-                             getenv("NL_NO_ATTN_FIN") != nullptr};
-    return k;
-}
-
 template <int HD, int G>
 void launch_attn_tile_g(const AttnParams &P, int n, int kvs, int nsplit, hipStream_t st) {
     constexpr int QT = AttnTileQT<G>::value;
-    const bool f32_tile = attn_knobs().f32_tile;
-    if (f32_tile) hipLaunchKernelGGL((attn_tile_kernel<HD, G, QT>), dim3(kvs, nsplit, (n + QT - 1) / QT), dim3(QT * G * 4), 0, st, P, n);
+    if (process_knobs().attn_f32) hipLaunchKernelGGL((attn_tile_kernel<HD, G, QT>), dim3(kvs, nsplit, (n + QT - 1) / QT), dim3(QT * G * 4), 0, st, P, n);
     else {
         constexpr int QT16 = AttnTile16QT<G>::value;
         if (P.live_map && P.kv16) hipLaunchKernelGGL((attn_tile16_kernel<HD, G, AttnTile16ShadowQT<G>::value, true>), dim3(nsplit /* = listed workgroups */), dim3(AttnTile16ShadowQT<G>::value * G * 4), 0, st, P, n);
@@ -664,7 +761,7 @@ BlockParams attn_block_params(nl_engine *e, int l, const float *x_in) {
     B.kcache = e->kcache + (long long)l * e->kv_layer_stride; B.vcache = e->vcache + (long long)l * e->kv_layer_stride;
     B.kv_stream_stride = e->kv_stream_stride; B.ctl = e->ctl;
     B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv; B.bias_out = L.bo; B.parts = e->parts;
-    B.xchg = e->xchg; B.tick = e->tick; B.layer_tag = (unsigned)(l + 1); B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->spin_limit;
+    B.xchg = e->xchg; B.tick = e->tick; B.layer_tag = (unsigned)(l + 1); B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->knobs.fused_spin_limit;
     return B;
 }
 
@@ -716,7 +813,7 @@ void build_plan_blocks(nl_engine *e, std::vector<Op> &plan) {
             F.D = c.dim; F.I = e->Is; F.npairs = L.gate.npairs;
             F.x = e->x[0]; F.normw = L.ffn_norm; F.parts_in = e->parts; F.nparts_in = e->Hs; F.x_out = e->x[1]; F.eps = c.rms_eps;
             F.parts_out = e->parts_ffn; F.xchg = e->xchg_ffn; F.tick = e->tick; F.layer_tag = (unsigned)(l + 1);
-            F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->spin_limit;
+            F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->knobs.fused_spin_limit;
             const int wt = L.gate.wtype, grid = ffn_grid(nslices);
             plan.push_back({K_FFNBLOCK, 0, nullptr, 0, [F, wt, grid, e](hipStream_t st) mutable {
                                    F.dbg = e->dbg_block;      // nl_debug_stamps only
@@ -753,7 +850,7 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
     plan.clear();
     const nl_config &c = e->cfg;
     const bool p2p = e->p2p.on;
-    const bool tp = (e->G > 1 || e->force_tp_plan) && !p2p;   // RCCL seams (or the in-process group's own sums)
+    const bool tp = (e->G > 1 || e->knobs.force_tp_plan) && !p2p;   // RCCL seams (or the in-process group's own sums)
     int cur = 0;
     int lm_blocks = 0, lm_spb = 1;
     const float *pending = nullptr;  // all-reduced partial still to be added to the residual stream
@@ -802,7 +899,7 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
         B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv;
         B.nsplit_max = e->nsplit_max;
         B.xchg = e->xchg; B.tick = p2p ? e->p2p.epoch : e->tick; B.layer_tag = (unsigned)(l + 1);
-        B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->spin_limit;
+        B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->knobs.fused_spin_limit;
         Q.wo_q = L.wo.q; Q.wo_s = L.wo.s; Q.wo_npairs = L.wo.npairs; Q.wo_ntiles = L.wo.ntiles; Q.wo_gshift = e->tpg.wo_gshift;
         Q.wo_tpw = e->tpg.wo_tpw;
         Q.n_heads_local = e->Hs; Q.xq = e->tp_xq; Q.xo = e->tp_xo; Q.bias_out = L.bo; Q.x = e->x[cur];
@@ -810,13 +907,13 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
         Q.seam = sm;
         const bool mfa = e->mf_attn;
         if (mfa) { B.qkv_q = L.qkv.q2; B.qkv_s = L.qkv.s2; }       // (WO stays on the vector pipe: nl_tp.h)
-        if (e->wide_ffn && (e->prefetch & 1) && L.gate.wtype == L.up.wtype && (L.gate.wtype == WT_Q4_0 || L.gate.wtype == WT_Q8_0)) {
+        if (e->wide_ffn && (e->knobs.prefetch & 1) && L.gate.wtype == L.up.wtype && (L.gate.wtype == WT_Q4_0 || L.gate.wtype == WT_Q8_0)) {
             Q.pf.q[0] = e->mf_ffn ? L.gate.q2 : L.gate.q; Q.pf.q[1] = e->mf_ffn ? L.up.q2 : L.up.q;
             Q.pf.s[0] = e->mf_ffn ? L.gate.s2 : L.gate.s; Q.pf.s[1] = e->mf_ffn ? L.up.s2 : L.up.s;
             Q.pf.tile_qbytes = tile_qbytes(L.gate.wtype, L.gate.npairs); Q.pf.tile_sbytes = tile_sbytes(L.gate.wtype, L.gate.npairs);
-            Q.pf.ntiles = L.gate.ntiles; Q.pf.nmat = 2; Q.pf.blocks = L.down.ntiles; Q.pf_early = (e->prefetch & 8) ? 1 : 0;
+            Q.pf.ntiles = L.gate.ntiles; Q.pf.nmat = 2; Q.pf.blocks = L.down.ntiles; Q.pf_early = (e->knobs.prefetch & 8) ? 1 : 0;
         }
-        if ((e->prefetch & 16) && Q.pf.nmat > 0 && l + 1 < c.n_layers) {
+        if ((e->knobs.prefetch & 16) && Q.pf.nmat > 0 && l + 1 < c.n_layers) {
             const nl_engine::Layer &N = e->layers[l + 1];
             if (N.qkv.wtype == WT_Q4_0 || N.qkv.wtype == WT_Q8_0) {
                 Q.pf2.q[0] = Q.pf2.q[1] = e->mf_attn ? N.qkv.q2 : N.qkv.q; Q.pf2.s[0] = Q.pf2.s[1] = e->mf_attn ? N.qkv.s2 : N.qkv.s;
@@ -852,14 +949,14 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
         F.rounds = (L.gate.ntiles + grid - 1) / grid;
         F.normw = L.ffn_norm; F.eps = c.rms_eps; F.x = e->x[cur]; F.hx = e->tp_hx;
         F.tick = p2p ? e->p2p.epoch : e->tick; F.layer_tag = (unsigned)(l + 1);
-        F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->spin_limit;
+        F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->knobs.fused_spin_limit;
         const int wt = L.gate.wtype, nf = e->wide_nf, ngc = e->wide_ngc, rounds = F.rounds;
         const size_t lds = wide_ffn_lds_bytes(nf, L.down.npairs);
         F.seam = sm;
         const bool mff = e->mf_ffn;
         if (mff) { F.gate_q = L.gate.q2; F.gate_s = L.gate.s2; F.up_q = L.up.q2; F.up_s = L.up.s2; F.dn_q = L.down.q2; F.dn_s = L.down.s2; }
-        F.pf_ahead = (e->prefetch & 4) ? 1 : 0;
-        if ((e->prefetch & 2) && fused && (e->fused_mode == 3 || e->fused_mode == 4) && l + 1 < c.n_layers) {
+        F.pf_ahead = (e->knobs.prefetch & 4) ? 1 : 0;
+        if ((e->knobs.prefetch & 2) && fused && (e->fused_mode == 3 || e->fused_mode == 4) && l + 1 < c.n_layers) {
             const nl_engine::Layer &N = e->layers[l + 1];
             if (N.qkv.wtype == WT_Q4_0 || N.qkv.wtype == WT_Q8_0) {
                 PfQkv &X = F.pf;
@@ -918,7 +1015,7 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
                 F.pair = e->tpg.pair; F.n_prod = e->tpg.n_prod; F.n_cons = e->tpg.n_cons; F.ct_shift = e->tpg.ct_shift;
                 F.normw = L.ffn_norm; F.eps = c.rms_eps; F.x = e->x[cur]; F.hx = e->tp_hx;
                 F.tick = p2p ? e->p2p.epoch : e->tick; F.layer_tag = (unsigned)(l + 1);
-                F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->spin_limit;
+                F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->knobs.fused_spin_limit;
                 F.seam = make_seam(seam++);
                 const int wt = L.gate.wtype, grid = e->tpg.grid, nf = e->tpg.nf, ngc = e->tpg.ngc, nr = e->tpg.nr;
                 const size_t lds = tp_ffn_lds_bytes(L.down.npairs);
@@ -976,7 +1073,7 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
             B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv;
             B.part_o = e->part_o; B.part_ml = e->part_ml; B.nsplit_max = e->nsplit_max;
             B.xchg = e->xchg; B.tick = p2p ? e->p2p.epoch : e->tick; B.layer_tag = (unsigned)(l + 1);
-            B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->spin_limit;
+            B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->knobs.fused_spin_limit;
             const int wt = L.qkv.wtype, grid = grp_grid(e->KVs, B.members);
             const int ngroups = (L.qkv.npairs + KL - 1) / KL, nf = (ngroups + 16 / e->grp_tpm - 1) / (16 / e->grp_tpm);
             plan.push_back({K_ATTNBLOCK, 0, nullptr, 0, [B, wt, grid, nf](hipStream_t st) {
@@ -1157,7 +1254,7 @@ int capture_graph(nl_engine *e, nl_engine::PlanSet &S) {
     if (s != hipSuccess) return e->fail(NL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(s));
     S.graph = g;
     HIPCK(e, hipGraphInstantiate(&S.exec, S.graph, nullptr, nullptr, 0));
-    if (e->d_box && e->G == 1 && !e->force_tp_plan && !e->p2p.on && !getenv("NL_NO_CALL_BOX")) {
+    if (e->d_box && e->G == 1 && !e->knobs.force_tp_plan && !e->p2p.on && e->knobs.call_box) {
         HIPCK(e, hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
         hipLaunchKernelGGL(box_fetch_kernel, dim3(1), dim3(64), 0, e->stream, e->d_box, e->ctl);
         const int rc3 = run_plan_eager(e, S);
@@ -1169,12 +1266,12 @@ int capture_graph(nl_engine *e, nl_engine::PlanSet &S) {
     }
     // chained greedy decode replays a graph that holds the plan 16 times: the gap between two graph launches
     // (~8 us on this stack) is then paid once per 16 tokens (nano 3834 -> 3945 tok/s; 4 steps: 3905; 32 / 64: as 16)
-    static const int steps = getenv("NL_GRAPH_STEPS") ? atoi(getenv("NL_GRAPH_STEPS")) : 16;   // developer knob (tools/)
-    if (steps > 1 && ((e->G == 1 && !e->force_tp_plan) || e->p2p.on)) {
+    const int steps = process_knobs().graph_steps;
+    if (steps > 1 && ((e->G == 1 && !e->knobs.force_tp_plan) || e->p2p.on)) {
         HIPCK(e, hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
         int rc2 = NL_OK;
         // step k's argmax also embeds step k+1's token (argmax_embed_kernel): the embed launch exists in step 0 only
-        static const bool fuse_embed = getenv("NL_NO_ARGMAX_EMBED") == nullptr;
+        const bool fuse_embed = process_knobs().argmax_embed;
         for (int k = 0; k < steps && !rc2; k++)
             for (const Op &op : S.ops) {
                 if (fuse_embed && op.kind == K_EMBED && k > 0) continue;
@@ -1260,7 +1357,7 @@ int build_all(nl_engine *e) {
     build_plan(e, e->ps[0].ops, false);
     if (e->fused) build_plan(e, e->ps[1].ops, true);
     if (e->fused && e->attn_helpers) build_plan(e, e->ps[2].ops, true, true);
-    const bool has_coll = (e->G > 1 || e->force_tp_plan) && !e->p2p.on;
+    const bool has_coll = (e->G > 1 || e->knobs.force_tp_plan) && !e->p2p.on;
     if (e->use_graph && !(e->cfg.flags & NL_FLAG_LOCAL_GROUP)) {
         for (int k = 0; k < (e->fused ? (e->attn_helpers ? 3 : 2) : 1); k++) {
             int rc = capture_graph(e, e->ps[k]);
@@ -1268,7 +1365,7 @@ int build_all(nl_engine *e) {
                 // RCCL inside a captured graph is not guaranteed on every RCCL build: fall back to eager launches
                 (void)hipGetLastError();
                 destroy_graphs(e->ps[k]);
-                if (!getenv("NL_QUIET")) fprintf(stderr, "[nanollama_hip] graph capture with RCCL failed (%s); using eager launches\n", e->err.c_str());
+                if (!e->knobs.quiet) fprintf(stderr, "[nanollama_hip] graph capture with RCCL failed (%s); using eager launches\n", e->err.c_str());
             } else if (rc) {
                 return rc;
             }
@@ -1335,7 +1432,7 @@ bool take_fused_timeout(nl_engine *e) {
     destroy_samp_graphs(e);
     e->fail(NL_OK, "warning: a fused-launch cluster exchange timed out (status %u); the step was redone on the general plan, "
                    "which this handle keeps from now on", st);
-    if (!getenv("NL_QUIET")) fprintf(stderr, "[nanollama_hip] %s\n", e->err.c_str());
+    if (!e->knobs.quiet) fprintf(stderr, "[nanollama_hip] %s\n", e->err.c_str());
     return true;
 }
 
@@ -1360,7 +1457,7 @@ void pd_free(nl_engine *e) {
 int pd_build(nl_engine *e) {
     nl_engine::Persist &d = e->pd;
     const nl_config &c = e->cfg;
-    bool ok = d.candidate && (e->embd_type == WT_Q8_0 || e->embd_type == WT_Q4_0 || e->embd_type == WT_Q5_0) && e->G == 1 && !e->force_tp_plan && e->num_cus == PD_GRID;
+    bool ok = d.candidate && (e->embd_type == WT_Q8_0 || e->embd_type == WT_Q4_0 || e->embd_type == WT_Q5_0) && e->G == 1 && !e->knobs.force_tp_plan && e->num_cus == PD_GRID;
     for (int l = 0; ok && l < c.n_layers; l++) {
         for (int i = 0; i < 7; i++) ok = ok && d.raw[l][i];
         const nl_engine::Layer &L = e->layers[l];
@@ -1430,12 +1527,8 @@ int pd_build(nl_engine *e) {
         d.candidate = false;
         return NL_OK;
     }
-    if (const char *mp = getenv("NL_PERSIST_MAX_POS")) d.max_pos = std::max(0, std::min(PD_MAX_POS, atoi(mp)));   // knob (tests, tools)
-    if (const char *sl = getenv("NL_PERSIST_SPIN_LIMIT")) d.spin_limit = atoi(sl);   // knob (tests): 0 makes every poll give up
-    if (const char *ss = getenv("NL_PERSIST_SESSION")) d.session_on = atoi(ss) != 0;  // knob (A/B): 0 = one launch per call
-    if (const char *iu = getenv("NL_PERSIST_IDLE_US")) d.idle_ticks = std::max(1LL, std::min(2000000LL, atoll(iu))) * 100;   // at most 2 s
-    if (!d.d_mail) d.session_on = false;
-    d.max_pos = std::min(d.max_pos, c.seq_len);
+    d.session_on = e->knobs.persist_session && d.d_mail;
+    d.max_pos = std::min(e->knobs.persist_max_pos, c.seq_len);
     d.tag_base = 0;
     d.ready = true;
     return NL_OK;
@@ -1461,9 +1554,9 @@ int pd_launch(nl_engine *e, int stream, int token, int pos, int n, float *host_l
     PdParams P{};
     P.census = d.census + (d.launch_no & 1u) * 16; P.census_next = d.census + ((d.launch_no + 1u) & 1u) * 16;
     d.launch_no++;
-    P.session = session ? 1 : 0; P.idle_ticks = d.idle_ticks; P.mbox = d.d_mail; P.host_done = d.d_mail ? d.d_mail + 8 : nullptr; P.gtok = d.gtok;
+    P.session = session ? 1 : 0; P.idle_ticks = e->knobs.persist_idle_ticks; P.mbox = d.d_mail; P.host_done = d.d_mail ? d.d_mail + 8 : nullptr; P.gtok = d.gtok;
     P.D = c.dim; P.I = c.interm; P.H = c.n_heads; P.V = c.vocab; P.L = c.n_layers; P.seq_len = c.seq_len; P.rope_conj = c.rope_conjugate;
-    P.n_steps = n; P.token0 = token; P.pos0 = pos; P.spin_limit = d.spin_limit;
+    P.n_steps = n; P.token0 = token; P.pos0 = pos; P.spin_limit = e->knobs.persist_spin_limit;
     P.eps = c.rms_eps; P.scale = (float)(1.0 / std::sqrt((double)e->hd));
     P.tag_base = d.tag_base;
     d.tag_base += (unsigned)n + 2u;
@@ -1491,10 +1584,9 @@ int pd_launch(nl_engine *e, int stream, int token, int pos, int n, float *host_l
 bool pd_take_timeout(nl_engine *e) {
     nl_engine::Persist &d = e->pd;
     if (!d.h_status) return false;
-    // (test knob, read per call: the first n launches of the handle are treated as census misses although they placed well --
-    //  the host side of the policy below is exercised without a crowded device)
-    const char *fk = getenv("NL_PERSIST_FAKE_CENSUS_MISS");
-    if (!*d.h_status && fk && d.launches > 0 && d.fake_misses < atoi(fk)) { d.fake_misses++; *d.h_status = 64u; }
+    // (test knob: the first n launches of the handle are treated as census misses although they placed well -- the host side of
+    //  the policy below is exercised without a crowded device)
+    if (!*d.h_status && d.launches > 0 && d.fake_misses < e->knobs.persist_fake_misses) { d.fake_misses++; *d.h_status = 64u; }
     if (!*d.h_status) return false;
     const unsigned st = *d.h_status;
     *d.h_status = 0;
@@ -1515,7 +1607,7 @@ bool pd_take_timeout(nl_engine *e) {
     e->fail(NL_OK, "warning: the persistent decode launch gave up (status %u: %s%s); the chunk was redone on the launch plans%s", st,
             (st & 64u) ? "its workgroups were not placed 32 per XCD" : "a hand-off poll timed out", seen,
             d.retired ? ", which this handle keeps from now on" : " (the next call tries the persistent launch again)");
-    if (!getenv("NL_QUIET")) fprintf(stderr, "[nanollama_hip] %s\n", e->err.c_str());
+    if (!e->knobs.quiet) fprintf(stderr, "[nanollama_hip] %s\n", e->err.c_str());
     return true;
 }
 
@@ -1647,14 +1739,10 @@ hipError_t launch_xsplit(int wtype, const float *x, int ldx, int cols, int n_tok
 // Long token runs over Q4_0 weights take the weights-through-LDS kernel (nl_qgemm2.h: 1.2-1.5x qgemm_kernel from 128
 // tokens up, tools/qgemm2_bench.hip; Q8_0's 32-byte rows cost more to expand and stay on qgemm_kernel).  Workgroups of
 // 64 rows: x 256 tokens (two token tiles per wavefront) when that still gives every compute unit two of them, else x 64.
-bool qgemm2_ok(int wtype, int n_tokens) {
-    const char *knob = getenv("NL_QG2_MIN_TOKENS");   // knob (tests, tools; read per launch so a test can flip it): a huge value disables
-    const int min_n = knob ? atoi(knob) : 128;
-    return wtype == WT_Q4_0 && n_tokens >= min_n;
-}
+bool qgemm2_ok(int wtype, int n_tokens, const StepKnobs &k) { return wtype == WT_Q4_0 && n_tokens >= k.qg2_min_tokens; }
 // the plain GEMM of a long Q4_0 token run whose unsplit 64-row x 64-token grid fills the chip: qgemm2_kernel, no split-K
-bool qgemm2_plain_unsplit(int wtype, int ntiles, int n_tokens) {
-    return qgemm2_ok(wtype, n_tokens) && ((ntiles + 3) / 4) * ((n_tokens + QG_TOK - 1) / QG_TOK) >= 128;
+bool qgemm2_plain_unsplit(int wtype, int ntiles, int n_tokens, const StepKnobs &k) {
+    return qgemm2_ok(wtype, n_tokens, k) && ((ntiles + 3) / 4) * ((n_tokens + QG_TOK - 1) / QG_TOK) >= 128;
 }
 template <int EPI>
 hipError_t launch_qgemm2(const QGemmParams &P, int row_blocks, hipStream_t st) {
@@ -1669,14 +1757,14 @@ hipError_t launch_qgemm2(const QGemmParams &P, int row_blocks, hipStream_t st) {
 // Worth it only when the unsplit grid fills the chip; the caller falls back to the plain launch + bswiglu otherwise.
 constexpr int QG_FUSED_WAVES = 4;
 bool qgemm_swiglu_fits(int ntiles, int n_tokens) {
-    static const int min_wg = getenv("NL_FUSED_SWIGLU_MIN_WG") ? atoi(getenv("NL_FUSED_SWIGLU_MIN_WG")) : 128;   // knob: tests force 1, tools disable with a huge value
+    const int min_wg = process_knobs().fused_swiglu_min_wg;
     // (a step of <= 32 tokens runs the plain kernel on one / two 16-token tiles instead: big x 8 streams 7.76 -> 7.55 ms)
     return (n_tokens > 32 || min_wg <= 1) && ((ntiles + QG_FUSED_WAVES - 1) / QG_FUSED_WAVES) * ((n_tokens + QG_TOK - 1) / QG_TOK) >= min_wg;
 }
-hipError_t launch_qgemm_swiglu(int wtype, QGemmParams P, hipStream_t st) {
+hipError_t launch_qgemm_swiglu(int wtype, QGemmParams P, const StepKnobs &k, hipStream_t st) {
     P.nt16 = ((P.n_tokens + 63) / 64) * 4;
     P.ksplit = 1;
-    if (qgemm2_ok(wtype, P.n_tokens)) return launch_qgemm2<QG_EPI_SWIGLU>(P, (P.ntiles + 1) / 2, st);
+    if (qgemm2_ok(wtype, P.n_tokens, k)) return launch_qgemm2<QG_EPI_SWIGLU>(P, (P.ntiles + 1) / 2, st);
     const dim3 grid((P.ntiles + QG_FUSED_WAVES - 1) / QG_FUSED_WAVES, (P.n_tokens + QG_TOK - 1) / QG_TOK, 1);
     switch (wtype) {
     case WT_Q4_0: hipLaunchKernelGGL((qgemm_kernel<WT_Q4_0, QG_FUSED_WAVES, 2, QG_EPI_SWIGLU>), grid, dim3(QG_FUSED_WAVES * 64), 0, st, P); break;
@@ -1690,13 +1778,12 @@ hipError_t launch_qgemm_swiglu(int wtype, QGemmParams P, hipStream_t st) {
 // Q|K|V GEMM with the RoPE + KV-store epilogue (nl_qgemm.h): 128-row workgroups, no split-K -- for steps whose
 // unsplit grid fills the chip (prompts); decode batches keep the split-K GEMM + brope_kv.
 bool qgemm_rope_fits(int ntiles, int n_tokens) {
-    static const int min_wg = getenv("NL_FUSED_ROPE_MIN_WG") ? atoi(getenv("NL_FUSED_ROPE_MIN_WG")) : 128;   // knob: tests force 1
-    return ((ntiles + QG_WAVES - 1) / QG_WAVES) * ((n_tokens + QG_TOK - 1) / QG_TOK) >= min_wg;
+    return ((ntiles + QG_WAVES - 1) / QG_WAVES) * ((n_tokens + QG_TOK - 1) / QG_TOK) >= process_knobs().fused_rope_min_wg;
 }
-hipError_t launch_qgemm_rope(int wtype, QGemmParams P, hipStream_t st) {
+hipError_t launch_qgemm_rope(int wtype, QGemmParams P, const StepKnobs &k, hipStream_t st) {
     P.nt16 = ((P.n_tokens + 63) / 64) * 4;
     P.ksplit = 1;
-    if (qgemm2_ok(wtype, P.n_tokens)) return launch_qgemm2<QG_EPI_ROPE>(P, (P.ntiles + 3) / 4, st);
+    if (qgemm2_ok(wtype, P.n_tokens, k)) return launch_qgemm2<QG_EPI_ROPE>(P, (P.ntiles + 3) / 4, st);
     P.row_groups = (P.ntiles + QG_WAVES - 1) / QG_WAVES;
     const dim3 grid(P.row_groups, (P.n_tokens + QG_TOK - 1) / QG_TOK, 1);
     switch (wtype) {
@@ -1711,8 +1798,7 @@ hipError_t launch_qgemm_rope(int wtype, QGemmParams P, hipStream_t st) {
 template <int WT, int WAVES, int RT = QG_RT>
 void launch_qgemm_nt(int nt, dim3 grid, hipStream_t st, const QGemmParams &P) {
     // one 64-token tile (decode batches, short prompts) in 64-row workgroups: fragments staged through registers (RSTAGE)
-    static const bool rstage_knob = !(getenv("NL_QG_RSTAGE") && atoi(getenv("NL_QG_RSTAGE")) == 0);   // developer knob (tools/)
-    if (WAVES == 4 && RT == 1 && grid.y == 1 && rstage_knob) {
+    if (WAVES == 4 && RT == 1 && grid.y == 1 && process_knobs().qg_rstage) {
         switch (nt) {
         case 1: hipLaunchKernelGGL((qgemm_kernel<WT, 4, 1, QG_EPI_PLAIN, 1, true>), grid, dim3(256), 0, st, P); break;
         case 2: hipLaunchKernelGGL((qgemm_kernel<WT, 4, 1, QG_EPI_PLAIN, 2, true>), grid, dim3(256), 0, st, P); break;
@@ -1727,13 +1813,13 @@ void launch_qgemm_nt(int nt, dim3 grid, hipStream_t st, const QGemmParams &P) {
     }
 }
 
-hipError_t launch_qgemm(int wtype, QGemmParams P, hipStream_t st, float *part_buf = nullptr, size_t part_cap = 0,
+hipError_t launch_qgemm(int wtype, QGemmParams P, const StepKnobs &k, hipStream_t st, float *part_buf = nullptr, size_t part_cap = 0,
                         int *ks_out = nullptr) {
     P.nt16 = ((P.n_tokens + 63) / 64) * 4;
     const int tok_tiles = (P.n_tokens + QG_TOK - 1) / QG_TOK;
     const int nchunks = (P.cols / 32 + QG_KC - 1) / QG_KC;
     const int mats = P.q1 ? 2 : 1;
-    if (qgemm2_plain_unsplit(wtype, P.ntiles, P.n_tokens) && mats == 1) {   // unsplit grid fills the chip
+    if (qgemm2_plain_unsplit(wtype, P.ntiles, P.n_tokens, k) && mats == 1) {   // unsplit grid fills the chip
         P.ksplit = 1;
         P.part = nullptr;
         if (ks_out) *ks_out = 1;
@@ -1743,28 +1829,24 @@ hipError_t launch_qgemm(int wtype, QGemmParams P, hipStream_t st, float *part_bu
     // Workgroup height: 128 rows (8 wavefronts) when that alone fills the chip, else 64 rows (4 wavefronts) --
     // twice the workgroups and half the split-K for the small-N decode batches (goldie shapes at 16-128 tokens:
     // -4...-18 % per launch, tools/qgemm_variants.sh); then split K until ~128 workgroups exist.
-    static const int force_waves = getenv("NL_QG_FORCE_WAVES") ? atoi(getenv("NL_QG_FORCE_WAVES")) : 0;   // developer knob
+    const ProcessKnobs &pk = process_knobs();
     int waves = QG_WAVES, rt = QG_RT;
     if (((P.ntiles + QG_WAVES - 1) / QG_WAVES) * mats * tok_tiles < 128) waves = 4;
-    if (force_waves == 4 || force_waves == 8) waves = force_waves;
+    if (pk.qg_force_waves == 4 || pk.qg_force_waves == 8) waves = pk.qg_force_waves;
     // decode batches (one 64-token tile): a workgroup's ingest is dominated by the activation fragments (256 B per
     // column against 72 B of Q4_0 weights for a 128-row workgroup), so tall workgroups -- 8 wavefronts x 2 tiles = 256
     // rows -- with a deep K split move the least data per launch
-    static const int dec_geom = getenv("NL_QG_DEC_GEOM") ? atoi(getenv("NL_QG_DEC_GEOM")) : 0;   // developer knob: 82 = 8 waves x 2 tiles
-    if (tok_tiles == 1 && part_buf && P.ldo == P.rows && dec_geom == 82 && QG_RT == 1) { waves = 8; rt = 2; }
+    if (tok_tiles == 1 && part_buf && P.ldo == P.rows && pk.qg_dec_geom == 82 && QG_RT == 1) { waves = 8; rt = 2; }
     const int row_groups = (P.ntiles + waves * rt - 1) / (waves * rt);
     P.row_groups = row_groups;
     int ks = 1;
     if (part_buf && P.ldo == P.rows) {
-        static const int ks_cap = getenv("NL_KS_CAP") ? atoi(getenv("NL_KS_CAP")) : 16;   // developer knob (tools/)
-        static const int min_wg = getenv("NL_QG_MIN_WG") ? atoi(getenv("NL_QG_MIN_WG")) : 128;
-        static const int max_chunks = getenv("NL_QG_MAX_CHUNKS") ? atoi(getenv("NL_QG_MAX_CHUNKS")) : 6;   // goldie x 64 streams: 2.06 -> 1.94 ms per step (tools/sweep_qg_split.sh)
-        static const int max_wg = getenv("NL_QG_MAX_WG") ? atoi(getenv("NL_QG_MAX_WG")) : 1024;
         // split K until the grid fills the chip; a decode batch (one token tile) keeps splitting while a workgroup would
-        // still walk more than max_chunks 128-column chunks one after the other (each is a dependent memory round trip)
-        while (ks * 2 <= nchunks && ks < ks_cap &&
-               (row_groups * mats * tok_tiles * ks < min_wg ||
-                (tok_tiles == 1 && (nchunks + ks - 1) / ks > max_chunks && row_groups * mats * ks * 2 <= max_wg)))
+        // still walk more than qg_max_chunks 128-column chunks one after the other (each is a dependent memory round trip;
+        // 6: goldie x 64 streams 2.06 -> 1.94 ms per step, tools/sweep_qg_split.sh)
+        while (ks * 2 <= nchunks && ks < pk.ks_cap &&
+               (row_groups * mats * tok_tiles * ks < pk.qg_min_wg ||
+                (tok_tiles == 1 && (nchunks + ks - 1) / ks > pk.qg_max_chunks && row_groups * mats * ks * 2 <= pk.qg_max_wg)))
             ks *= 2;
         while (ks > 1 && (size_t)ks * P.n_tokens * P.ldo > part_cap) ks /= 2;
     }
@@ -1808,17 +1890,15 @@ hipError_t launch_dgemm_head(const QGemmParams &P, hipStream_t st, int num_cus) 
 
 namespace {
 
-// below this many tokens the ~10 launches per layer of the multi-token step cost more than n single-token steps
-// (measured: 2 streams nano 0.61 ms batched vs 0.55 ms as two single steps, goldie 1.77 vs 1.47; 3 streams 0.61 vs
+// (the multi-token step takes n >= NL_BATCH_MIN tokens, 3: below that its ~10 launches per layer cost more than n single-token
+// steps -- measured: 2 streams nano 0.61 ms batched vs 0.55 ms as two single steps, goldie 1.77 vs 1.47; 3 streams 0.61 vs
 // 0.82 and 1.77 vs 2.19)
-const int NL_BATCH_MIN = getenv("NL_BATCH_MIN") ? atoi(getenv("NL_BATCH_MIN")) : 3;   // env: developer knob (tools/)
-
 bool batch_supported(const nl_engine *e) {
-    if (e->G != 1 || e->force_tp_plan) return false;
+    if (e->G != 1 || e->knobs.force_tp_plan) return false;
     auto ok = [](const PackedMat &m) { return m.wtype == WT_Q4_0 || m.wtype == WT_Q8_0 || m.wtype == WT_F16; };
     for (const auto &L : e->layers)
         if (!ok(L.qkv) || !ok(L.wo) || !ok(L.gate) || !ok(L.up) || !ok(L.down)) return false;
-    return ok(e->lm_head) && !getenv("NL_NO_BATCH_PATH");
+    return ok(e->lm_head) && e->knobs.batch_path;
 }
 
 int batch_alloc(nl_engine *e, nl_engine::Batch &b, int cap_limit = 2048) {
@@ -1889,10 +1969,10 @@ bool dgemm_model_ok(const nl_engine *e) {
 }
 // the block-major weight copies dgemm_kernel reads, once per handle, at its first multi-token step (outside any capture; the
 // caller holds g_setup_mu)
-int dgemm_prepare(nl_engine *e) {
+int dgemm_prepare(nl_engine *e, const StepKnobs &k) {
     if (e->dg_state) return NL_OK;
     e->dg_state = -1;
-    if (getenv("NL_DGEMM") && atoi(getenv("NL_DGEMM")) == 0) { e->dg_state = 0; return NL_OK; }     // (knob: looked at again next step)
+    if (!k.dgemm) { e->dg_state = 0; return NL_OK; }     // (NL_DGEMM=0: looked at again next step)
     if (!batch_supported(e) || !dgemm_model_ok(e)) return NL_OK;
     for (auto &L : e->layers)
         for (PackedMat *m : {&L.qkv, &L.wo, &L.gate, &L.up, &L.down}) {
@@ -1922,12 +2002,9 @@ int dgemm_prepare(nl_engine *e) {
     e->dg_state = 1;
     return NL_OK;
 }
-bool dgemm_step_ok(const nl_engine *e, int n) {
-    if (e->dg_state != 1) return false;
-    const char *k = getenv("NL_DGEMM");                 // knob (tests, tools; read per step): 0 keeps the split-K launches
-    if (k && atoi(k) == 0) return false;
-    const char *mk = getenv("NL_DGEMM_MAX_TOKENS");
-    if (mk) return n <= atoi(mk);
+bool dgemm_step_ok(const nl_engine *e, int n, const StepKnobs &k) {
+    if (e->dg_state != 1 || !k.dgemm) return false;
+    if (k.dgemm_max_tokens) return n <= *k.dgemm_max_tokens;
     // Decode batches and prompts while the largest launch (gate || up: ceil(n / 16) token tiles x I / 64 row groups) stays within
     // about four rounds of workgroups: measured ahead of the long-run GEMM of nl_qgemm2.h up to 256 tokens on goldie (768 / 1024
     // workgroups: 2.77 against 2.88 ms, 3.23 against 3.21) and 512 on mini (1.60 against 1.74 ms; 768 tokens 2.21 against 2.19) --
@@ -1938,31 +2015,32 @@ bool dgemm_step_ok(const nl_engine *e, int n) {
 // GEMM of the multi-token step: input = the fragment store the producing kernel just filled; output = `out`
 // (with resid / bias applied) when it ran unsplit, else split-K slabs in `part` for the consumer to add.
 hipError_t qg(nl_engine *e, nl_engine::Batch &bt, const PackedMat &m, int n, float *out, int ldo, const float *resid, hipStream_t st,
-              GemmOut *res, float *part, const float *bias = nullptr, const uint4 *xf = nullptr,
-              const QGemmParams::NormOut *nout = nullptr, int x1 = 0) {
+              const StepKnobs &k, GemmOut *res, float *part, const float *bias = nullptr, const uint4 *xf = nullptr,
+              const QGemmParams::NormOut *nout = nullptr) {
     QGemmParams P{};
     P.bias = bias;
-    P.x1 = x1;
+    P.x1 = k.x1_gemm();
     if (nout) P.nrm_out = *nout;
     P.q = m.q; P.s = m.s; P.rows = m.rows; P.cols = m.cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
     P.xf = xf ? xf : bt.xfrag; P.n_tokens = n; P.out = out; P.ldo = ldo; P.resid = resid;
     int ks = 1;
-    hipError_t s = launch_qgemm(m.wtype, P, st, part, bt.kpart_cap, &ks);
+    hipError_t s = launch_qgemm(m.wtype, P, k, st, part, bt.kpart_cap, &ks);
     *res = GemmOut{out, part, ks, (long long)n * ldo, bias};
     return s;
 }
 
-hipError_t launch_qgemm_plain(nl_engine *e, nl_engine::Batch &bt, const PackedMat &m, int n, float *out, int ldo, hipStream_t st) {
+hipError_t launch_qgemm_plain(nl_engine *e, nl_engine::Batch &bt, const PackedMat &m, int n, float *out, int ldo, const StepKnobs &k,
+                              hipStream_t st) {
     QGemmParams P{};
     P.q = m.q; P.s = m.s; P.rows = m.rows; P.cols = m.cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
     P.xf = bt.xfrag; P.n_tokens = n; P.out = out; P.ldo = ldo;
-    return launch_qgemm(m.wtype, P, st, bt.kpart, bt.kpart_cap);   // split-K + its own sum launch
+    return launch_qgemm(m.wtype, P, k, st, bt.kpart, bt.kpart_cap);   // split-K + its own sum launch
 }
 
 // One multi-token step: n <= 64 (token, pos, stream) triples through every layer on the MFMA path.
 // lm_mode: 0 = no LM head, 1 = logits + argmax for every token, 2 = logits + argmax for the LAST token only.
 // The caller has filled bt.h_meta; stream-ordered, no synchronisation inside.
-int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int lm_mode, bool one_stream = false) {
+int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int lm_mode, const StepKnobs &k, bool one_stream = false) {
     const nl_config &c = e->cfg;
     const int D = c.dim, hd = e->hd, HQ = e->Hs * hd, R = (e->Hs + 2 * e->KVs) * hd;
 #define LCK(expr) do { hipError_t s_ = (expr); if (s_ != hipSuccess) return e->fail(NL_ERR_HIP, "batched step: %s: %s", #expr, hipGetErrorString(s_)); } while (0)
@@ -1974,17 +2052,15 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     int n_live = 0, max_nparts = 0;
     bool kv16_on = false;
     {
-        bool cons = one_stream && n >= 8 && attn_tile_supported(e->gqa) && !attn_knobs().f32_tile && !attn_knobs().no_tile;
+        bool cons = one_stream && n >= 8 && attn_tile_supported(e->gqa) && !process_knobs().attn_f32 && !process_knobs().no_attn_tile;
         for (int i = 1; i < n && cons; i++) cons = b.h_meta[b.cap + i] == b.h_meta[b.cap] + i;
-        const int kv16_min = getenv("NL_KV16_MIN_TOKENS") ? atoi(getenv("NL_KV16_MIN_TOKENS")) : 256;   // (read per step: a test lowers it)
-        kv16_on = cons && n >= kv16_min && b.kv16 != nullptr;
+        kv16_on = cons && n >= k.kv16_min_tokens && b.kv16 != nullptr;
         const int qt = attn_tile16_qt(e->gqa) * (kv16_on ? 2 : 1), ntile = (n + qt - 1) / qt, p0 = b.h_meta[b.cap];
         const long long slots = (long long)e->num_cus * (kv16_on ? 1 : 2);   // workgroups resident at once
         if (cons && ntile <= 256 && e->KVs <= 255) {
             auto chunks_of = [&](int z) { return std::min((p0 + std::min((z + 1) * qt, n) - 1) / ATT_CH + 1, e->nsplit_max); };
-            const int run_knob = getenv("NL_ATT_RUN") ? atoi(getenv("NL_ATT_RUN")) : 0;   // developer knob: fixed run length (read per step: a test sets it)
-            int run = run_knob > 0 ? run_knob : 1;
-            for (; run_knob <= 0 && run < e->nsplit_max; run++) {
+            int run = k.att_run > 0 ? k.att_run : 1;     // (NL_ATT_RUN: a fixed run length)
+            for (; k.att_run <= 0 && run < e->nsplit_max; run++) {
                 long long wgs = 0;
                 for (int z = 0; z < ntile; z++) wgs += (chunks_of(z) + run - 1) / run;
                 if (wgs * e->KVs <= slots) break;
@@ -2019,7 +2095,7 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     const int nt16 = ((n + 63) / 64) * 4;
     // position splits any token of this step can see: the attention grids skip the rest (a decode batch at short
     // contexts would otherwise dispatch 15 empty workgroups for every live one)
-    const bool no_tile = attn_knobs().no_tile, no_fin = attn_knobs().no_fin;
+    const bool no_tile = process_knobs().no_attn_tile, no_fin = process_knobs().no_attn_fin;
     int nsplit = 1;
     for (int i = 0; i < n; i++) nsplit = std::max(nsplit, b.h_meta[b.cap + i] / ATT_CH + 1);
     bool consecutive = true;   // positions pos0, pos0 + 1, ...: a prompt
@@ -2027,36 +2103,25 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     nsplit = std::min(nsplit, e->nsplit_max);
     const bool tile_attn = one_stream && n >= 8 && attn_tile_supported(e->gqa) && !no_tile;   // prompts: attn_tile16_kernel
     const bool fin_attn = !tile_attn && nsplit == 1 && !no_fin;                                 // one split: attn_kernel<..., FIN>
-    const char *rk = getenv("NL_ROPE_IN_ATTN");    // knob (tests, tools; read per step): 0 keeps the brope_kv launch
-    const bool rope_attn_knob = !(rk && atoi(rk) == 0);
     GemmOut pend{nullptr, nullptr, 1, 0, nullptr};   // GEMM output not yet folded into the residual stream
     // RMSNorm folded around the GEMMs (QGemmParams::NormOut / NormIn): when WO and down run unsplit on qgemm2_kernel and
     // their consumers are the fused-epilogue GEMMs of the same kernel -- a Q4_0 prompt -- the producing GEMM writes the
     // next GEMM's fragments and per-block sums of squares itself and the two bnorm launches per layer disappear (mini,
     // 2047 tokens: 2 x 8.7 us of 187 us per layer).  Fragment stores then alternate: the consumer of a producing GEMM
     // reads xfrag2, everything else xfrag.
-    const char *fk = getenv("NL_FOLD_NORM");   // knob (tests, tools; read per step so a test can flip it): 0 keeps the bnorm launches
-    const bool fold_knob = !(fk && atoi(fk) == 0);
-    const bool dg = dgemm_step_ok(e, n);      // short token runs (decode batches): nl_dgemm.h, always folded
-    // ... and the LM head of a step that wants every token's logits (knob NL_DGEMM_HEAD=0, read per step: the split-K launches)
-    const bool dg_head = dg && lm_mode == 1 && e->dg_head && n <= b.lm_cap && (size_t)n * e->lm_head.ntiles * 2 <= b.kpart_cap &&
-                         !(getenv("NL_DGEMM_HEAD") && atoi(getenv("NL_DGEMM_HEAD")) == 0);
-    bool fold = fold_knob && !c.qk_norm && D % 64 == 0 && c.n_layers > 0;
+    const bool dg = dgemm_step_ok(e, n, k);      // short token runs (decode batches): nl_dgemm.h, always folded
+    // ... and the LM head of a step that wants every token's logits (NL_DGEMM_HEAD=0: the split-K launches)
+    const bool dg_head = dg && lm_mode == 1 && e->dg_head && n <= b.lm_cap && (size_t)n * e->lm_head.ntiles * 2 <= b.kpart_cap && k.dgemm_head;
+    bool fold = k.fold_norm && !c.qk_norm && D % 64 == 0 && c.n_layers > 0;
     for (int l = 0; l < c.n_layers && fold; l++) {
         const nl_engine::Layer &L = e->layers[l];
-        fold = qgemm2_plain_unsplit(L.wo.wtype, L.wo.ntiles, n) && qgemm2_plain_unsplit(L.down.wtype, L.down.ntiles, n) &&
+        fold = qgemm2_plain_unsplit(L.wo.wtype, L.wo.ntiles, n, k) && qgemm2_plain_unsplit(L.down.wtype, L.down.ntiles, n, k) &&
                L.wo.ntiles % 4 == 0 && L.down.ntiles % 4 == 0 &&
-               qgemm2_ok(L.qkv.wtype, n) && qgemm_rope_fits(L.qkv.ntiles, n) &&
-               L.up.wtype == L.gate.wtype && qgemm2_ok(L.gate.wtype, n) && qgemm_swiglu_fits(L.gate.ntiles, n);
+               qgemm2_ok(L.qkv.wtype, n, k) && qgemm_rope_fits(L.qkv.ntiles, n) &&
+               L.up.wtype == L.gate.wtype && qgemm2_ok(L.gate.wtype, n, k) && qgemm_swiglu_fits(L.gate.ntiles, n);
     }
     if (dg) fold = true;
     const int nrb = dg ? D / 32 : D / 64;      // partial sums of squares per token
-    // NL_PREFILL_PRECISION=fp16x1 (read per step: tests and bench.py flip it): the long-prompt GEMMs (qgemm2_kernel) and the
-    // prompt attention multiply only the fp16 hi half of every activation / probability -- half / a third of the matrix work,
-    // activations rounded to 11 bits.  The default x = hi + lo keeps float32-grade results (logit tolerance 1e-4).
-    const char *pk = getenv("NL_PREFILL_PRECISION");
-    const int x1 = pk && std::string(pk) == "fp16x1" ? 1 : 0;
-    const int x1_gemm = x1 || (pk && std::string(pk) == "fp16x1-gemm"), x1_attn = x1 || (pk && std::string(pk) == "fp16x1-attn");   // (developer: one half of the mode)
     // (pre-scales: the attention norm's consumer undoes sA and leaves sB for the WO producer; the feed-forward norm's consumer
     //  undoes sB and leaves sA for the down producer; layer 0's unfolded attention norm leaves the first sB)
     float *const sA = b.nscale, *const sB = b.nscale + b.cap;
@@ -2086,18 +2151,18 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             const PackedMat &m = L.qkv;
             P.q = dg ? m.q3 : m.q; P.s = dg ? m.s3 : m.s; P.rows = m.rows; P.cols = m.cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
             P.xf = folded_in ? b.xfrag2 : b.xfrag; P.nrm_in = folded_in ? nin_attn : nin_off;
-            P.n_tokens = n; P.ldo = (int)R; P.x1 = x1_gemm;
+            P.n_tokens = n; P.ldo = (int)R; P.x1 = k.x1_gemm();
             P.rope = QGemmParams::Rope{b.pos, b.stream, e->rope_cos, e->rope_sin, b.q, kc, vc, e->kv_stream_stride,
                                        L.bq, L.bk, L.bv, hd, e->Hs, e->KVs, c.seq_len, c.rope_conjugate, b.tcos, b.tsin, b.tkv};
-            LCK(dg ? launch_dgemm_rope(P, st) : launch_qgemm_rope(m.wtype, P, st));
+            LCK(dg ? launch_dgemm_rope(P, st) : launch_qgemm_rope(m.wtype, P, k, st));
         } else {
-            LCK(qg(e, b, L.qkv, n, b.qkv, R, nullptr, st, &qkv_out, b.kpart, nullptr, nullptr, nullptr, x1_gemm));
+            LCK(qg(e, b, L.qkv, n, b.qkv, R, nullptr, st, k, &qkv_out, b.kpart));
             // decode batches (every token its own stream: no token of the step attends over another's K / V row), no QK-norm:
             // the attention launch rotates and stores its own q / k / v rows (attn_rope_prologue) -- no brope_kv launch.
             // Below position 128 that is the one-split FIN kernel; with two splits per token every split rotates q and the
             // last one k / v.  Beyond that the repeated q work of every split costs more than the launch it saves (goldie x
             // 64 streams: positions 130..145 2.03 -> 1.92 ms per step, 300.. 2.19 -> 2.19, 1000.. 2.85 -> 2.95).
-            rope_in_attn = !tile_attn && nsplit <= 2 && !one_stream && !c.qk_norm && rope_attn_knob;
+            rope_in_attn = !tile_attn && nsplit <= 2 && !one_stream && !c.qk_norm && k.rope_in_attn;
             if (!rope_in_attn) {
                 const GemmOut &qkv = qkv_out;
                 BRopeParams P{qkv, R, hd, e->Hs, e->KVs, c.seq_len, c.rope_conjugate, c.qk_norm, c.rms_eps, b.pos, b.stream,
@@ -2117,7 +2182,7 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             if (one_stream && n >= 8 && attn_tile_supported(e->gqa) && !no_tile) {
                 // prefill: the step's tokens share a stream -> K/V split staged once per tile of tokens, fp16 MFMA with hi/lo-split operands (attn_tile16_kernel)
                 AttnParams T = P;
-                T.x1 = x1_attn;
+                T.x1 = k.x1_attn();
                 T.single_stream = c.max_streams == 1 ? 1 : 0;
                 T.pos_base_valid = consecutive ? 1 : 0;   // (a prompt: the kernel derives its key range without reading bpos)
                 T.pos_base = b.h_meta[b.cap];
@@ -2172,9 +2237,9 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             LCK(dg_plain(L.wo, b.xfrag, L.bo, &nout));
         } else if (fold) {
             const QGemmParams::NormOut nout{L.ffn_norm, b.xfrag2, b.ssq, sB};
-            LCK(qg(e, b, L.wo, n, b.x, D, b.x, st, &pend, b.kpart, L.bo, nullptr, &nout, x1_gemm));
+            LCK(qg(e, b, L.wo, n, b.x, D, b.x, st, k, &pend, b.kpart, L.bo, nullptr, &nout));
         } else {
-            LCK(qg(e, b, L.wo, n, b.x, D, b.x, st, &pend, b.kpart, L.bo, nullptr, nullptr, x1_gemm));
+            LCK(qg(e, b, L.wo, n, b.x, D, b.x, st, k, &pend, b.kpart, L.bo));
             LCK(norm(L.ffn_norm, L.gate, 0, n));
         }
         if (L.up.wtype != L.gate.wtype)   // (a mixed-type file: the fragment k-slot order differs per type)
@@ -2187,10 +2252,10 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             const PackedMat &m = L.gate;
             P.q = dg ? m.q3 : m.q; P.s = dg ? m.s3 : m.s; P.rows = m.rows; P.cols = m.cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
             P.xf = fold ? b.xfrag2 : b.xfrag; P.nrm_in = fold ? nin_ffn : nin_off;
-            P.n_tokens = n; P.ldo = e->Is; P.x1 = x1_gemm;
+            P.n_tokens = n; P.ldo = e->Is; P.x1 = k.x1_gemm();
             P.q1 = dg ? L.up.q3 : L.up.q; P.s1 = dg ? L.up.s3 : L.up.s;
             P.xf_out = fold ? b.xfrag : b.xfrag2; P.out_q4 = L.down.wtype == WT_Q4_0 ? 1 : 0;
-            LCK(dg ? launch_dgemm_swiglu(P, st) : launch_qgemm_swiglu(m.wtype, P, st));
+            LCK(dg ? launch_dgemm_swiglu(P, st) : launch_qgemm_swiglu(m.wtype, P, k, st));
             down_in = P.xf_out;
         } else {
             GemmOut gate, up;
@@ -2198,10 +2263,10 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
                 QGemmParams P{};
                 const PackedMat &m = L.gate;
                 P.q = m.q; P.s = m.s; P.rows = m.rows; P.cols = m.cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
-                P.xf = b.xfrag; P.n_tokens = n; P.out = b.g; P.ldo = e->Is; P.x1 = x1_gemm;
+                P.xf = b.xfrag; P.n_tokens = n; P.out = b.g; P.ldo = e->Is; P.x1 = k.x1_gemm();
                 P.q1 = L.up.q; P.s1 = L.up.s; P.out1 = b.u; P.part1 = b.kpart2;
                 int ks = 1;
-                LCK(launch_qgemm(m.wtype, P, st, b.kpart, b.kpart_cap, &ks));
+                LCK(launch_qgemm(m.wtype, P, k, st, b.kpart, b.kpart_cap, &ks));
                 gate = GemmOut{b.g, b.kpart, ks, (long long)n * e->Is, nullptr};
                 up = GemmOut{b.u, b.kpart2, ks, (long long)n * e->Is, nullptr};
             }
@@ -2218,9 +2283,9 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
         } else if (fold && l + 1 < c.n_layers) {
             const nl_engine::Layer &Ln = e->layers[l + 1];
             const QGemmParams::NormOut nout{Ln.attn_norm, b.xfrag2, b.ssq, sA};
-            LCK(qg(e, b, L.down, n, b.x, D, b.x, st, &pend, b.kpart, nullptr, down_in, &nout, x1_gemm));
+            LCK(qg(e, b, L.down, n, b.x, D, b.x, st, k, &pend, b.kpart, nullptr, down_in, &nout));
         } else {
-            LCK(qg(e, b, L.down, n, b.x, D, b.x, st, &pend, b.kpart, nullptr, down_in, nullptr, x1_gemm));
+            LCK(qg(e, b, L.down, n, b.x, D, b.x, st, k, &pend, b.kpart, nullptr, down_in));
         }
     }
     if (lm_mode) {
@@ -2238,13 +2303,52 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             hipLaunchKernelGGL(dg_argmax_kernel, dim3(n), dim3(1024), 0, st, reinterpret_cast<const uint2 *>(b.kpart), m.ntiles, b.ids);
         } else {
             LCK(norm(e->output_norm, e->lm_head, first, cnt));
-            LCK(launch_qgemm_plain(e, b, e->lm_head, cnt, b.logits, c.vocab, st));
+            LCK(launch_qgemm_plain(e, b, e->lm_head, cnt, b.logits, c.vocab, k, st));
             hipLaunchKernelGGL(bargmax_kernel, dim3(cnt), dim3(1024), 0, st, b.logits, c.vocab, b.ids);
         }
         LCK(hipGetLastError());
     }
 #undef LCK
     return NL_OK;
+}
+
+// One decode-batch step of m streams on stream st: their (token, position, stream) into the pinned block behind b.h_meta, then the
+// step as a hipGraph from `graphs` cached by (m, position splits, step knobs) -- it reads its tokens / positions / streams from that
+// block (a copy node), so one graph serves every step of that geometry.  The 150+ launches of a step are 3 us each when a host
+// thread queues them one by one -- more than the kernels of a decode batch.  A step whose capture fails runs eagerly.
+int decode_step(nl_engine *e, nl_engine::Batch &b, std::vector<nl_engine::StepGraph> &graphs, hipStream_t st, const int *streams,
+                const int *tokens, const int *pos, int m, const StepKnobs &k) {
+    int nsplit = 1;
+    for (int i = 0; i < m; i++) {
+        b.h_meta[i] = tokens[i];
+        b.h_meta[b.cap + i] = pos[i];
+        b.h_meta[2 * b.cap + i] = streams[i];
+        nsplit = std::max(nsplit, pos[i] / ATT_CH + 1);
+    }
+    hipGraphExec_t exec = nullptr;
+    for (const auto &G : graphs)
+        if (G.m == m && G.nsplit == nsplit && G.knobs == k) exec = G.exec;
+    if (!exec && e->use_graph) {
+        std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
+        hipGraph_t gr = nullptr;
+        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const int rc = batched_step(e, b, st, m, 1, k);
+            const hipError_t ce = hipStreamEndCapture(st, &gr);
+            if (!rc && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess) graphs.push_back({m, nsplit, k, gr, exec});
+            else { if (gr) (void)hipGraphDestroy(gr); exec = nullptr; }
+        }
+        (void)hipGetLastError();
+    }
+    if (!exec) return batched_step(e, b, st, m, 1, k);
+    HIPCK(e, hipGraphLaunch(exec, st));
+    return NL_OK;
+}
+
+// every cached decode-batch step graph, whole-batch and sub-batch (they hold the device pointers of the step)
+void destroy_step_graphs(nl_engine *e) {
+    auto drop = [](std::vector<nl_engine::StepGraph> &gs) { for (auto &G : gs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); } gs.clear(); };
+    drop(e->bt_graphs);
+    for (auto &sb : e->sub) drop(sb.graphs);
 }
 
 }  // namespace
@@ -2412,16 +2516,9 @@ int nl_create(const nl_config *cfg, nl_handle *out) {
     e->Hs = c.n_heads / e->G; e->KVs = c.n_kv_heads / e->G; e->Is = c.interm / e->G; e->Vs = c.vocab / e->G;
     e->nsplit_max = (c.seq_len + ATT_CH - 1) / ATT_CH;
     e->layers.resize(c.n_layers);
-    e->use_graph = !(c.flags & NL_FLAG_NO_GRAPH) && !getenv("NL_NO_GRAPH");
-    if (getenv("NL_FORCE_TP_PLAN")) e->force_tp_plan = true;
-    {
-        const char *pk = getenv("NL_PERSIST");      // knob (tests, tools): 0 keeps the launch plans for greedy chains too
-        e->pd.candidate = !(pk && atoi(pk) == 0) && c.tp_size == 1 && !(c.flags & NL_FLAG_LOCAL_GROUP) && !c.qk_norm &&
-                          pd_shape_ok(c.dim, c.interm, c.n_heads, c.n_kv_heads, c.head_dim, c.vocab, c.n_layers);
-    }
-    if (const char *v = getenv("NL_SUB_BATCHES")) e->sub_batches = std::max(1, std::min(4, atoi(v)));   // knob (tests, tools)
-    if (const char *v = getenv("NL_TW")) e->tw_override = atoi(v);
-    if (const char *v = getenv("NL_KW")) e->kw_override = atoi(v);
+    e->use_graph = !(c.flags & NL_FLAG_NO_GRAPH) && !e->knobs.no_graph;
+    e->pd.candidate = e->knobs.persist && c.tp_size == 1 && !(c.flags & NL_FLAG_LOCAL_GROUP) && !c.qk_norm &&
+                      pd_shape_ok(c.dim, c.interm, c.n_heads, c.n_kv_heads, c.head_dim, c.vocab, c.n_layers);
     if ((s = hipSetDevice(e->dev)) != hipSuccess || (s = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess ||
         (s = hipEventCreate(&e->ev0)) != hipSuccess || (s = hipEventCreate(&e->ev1)) != hipSuccess) {
         g_create_error = std::string("device init: ") + hipGetErrorString(s);
@@ -2792,7 +2889,7 @@ int nl_finalize(nl_handle e) {
     HIPCK(e, hipHostMalloc((void **)&e->h_logits, ((size_t)c.vocab + 4) * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));   // (the resident session's LM-head units store logits straight into it)
     e->d_h_logits = nullptr;
     if (hipHostGetDevicePointer((void **)&e->d_h_logits, e->h_logits, 0) != hipSuccess) { (void)hipGetLastError(); e->d_h_logits = nullptr; }
-    if (getenv("NL_NO_HOST_LOGITS")) e->d_h_logits = nullptr;      // knob (A/B): the DMA read-back
+    if (!e->knobs.host_logits) e->d_h_logits = nullptr;      // (NL_NO_HOST_LOGITS: the DMA read-back)
     e->ctl_ring_cap = std::max(c.seq_len, c.max_streams);
     HIPCK(e, hipHostMalloc((void **)&e->h_ctl_ring, (size_t)e->ctl_ring_cap * CTL_WORDS * sizeof(int), hipHostMallocDefault));
     memset(e->h_ctl_ring, 0, (size_t)e->ctl_ring_cap * CTL_WORDS * sizeof(int));       // (the callers fill five of the eight words)
@@ -2803,18 +2900,13 @@ int nl_finalize(nl_handle e) {
     {
         // fused attention block (nl_block.h): every layer must have its per-head WO slices, and the models it pays
         // for are the ones whose per-head weights are small (see the header of nl_block.h)
-        {
-            hipDeviceProp_t prop{};
-            if (hipGetDeviceProperties(&prop, e->dev) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
-            if (const char *sl = getenv("NL_FUSED_SPIN_LIMIT")) e->spin_limit = atoi(sl);   // knob (tests): 0 makes every exchange give up
-            if (const char *pf = getenv("NL_PREFETCH")) e->prefetch = atoi(pf);              // knob (A/B): bits of nl_engine::prefetch
-        }
-        const char *fa = getenv("NL_FUSED_ATTN");          // knob (tests, tools): 0 keeps the five-launch plan only, 2 forces mode 2
-        const int want = fa ? atoi(fa) : -1;
+        hipDeviceProp_t prop{};
+        if (hipGetDeviceProperties(&prop, e->dev) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
+        const int want = e->knobs.fused_attn;
         const bool base_ok = !(c.flags & NL_FLAG_LOCAL_GROUP) && want != 0 && e->hd == 64;
-        bool ok1 = base_ok && want != 2 && e->G == 1 && !e->force_tp_plan && c.dim % (BLK_MEMBERS * TR) == 0 && c.n_layers < 255;
+        bool ok1 = base_ok && want != 2 && e->G == 1 && !e->knobs.force_tp_plan && c.dim % (BLK_MEMBERS * TR) == 0 && c.n_layers < 255;
         // (an RCCL plan carries the all-reduced partial into the next projection's prologue, which the fused launch lacks)
-        bool ok2 = base_ok && c.n_layers < 255 && ((e->G == 1 && !e->force_tp_plan) || e->p2p.on);
+        bool ok2 = base_ok && c.n_layers < 255 && ((e->G == 1 && !e->knobs.force_tp_plan) || e->p2p.on);
         // mode 3 (nl_tp.h): a tensor-parallel rank's layer as two launches -- ranks of a push group, or the shards of an
         // in-process group that asked for it (NL_FLAG_GROUP_FUSED: the same kernels, the group adds the partials itself)
         const bool group_fused = (c.flags & NL_FLAG_LOCAL_GROUP) && (c.flags & NL_FLAG_GROUP_FUSED);
@@ -2822,14 +2914,12 @@ int nl_finalize(nl_handle e) {
         // together.  NL_WIDE_FFN: 0 = never, 2 = also when its grid does not fill the chip (tests at small shapes)
         auto wide_ffn_ok = [&]() {
             const nl_engine::Layer &L0 = e->layers[0];
-            const char *wf = getenv("NL_WIDE_FFN");
-            const int wfv = wf ? atoi(wf) : 1;
             const int ngroups = (L0.gate.npairs + KL - 1) / KL, dgroups = (L0.down.npairs + KL - 1) / KL;
-            bool okw = wfv != 0 && ngroups <= 16 && dgroups <= 48 && L0.gate.ntiles * GPT <= 5 * TP_THREADS && L0.down.ntiles <= e->num_cus &&
+            bool okw = e->knobs.wide_ffn != 0 && ngroups <= 16 && dgroups <= 48 && L0.gate.ntiles * GPT <= 5 * TP_THREADS && L0.down.ntiles <= e->num_cus &&
                        (L0.gate.ntiles + L0.down.ntiles - 1) / L0.down.ntiles <= 4 &&          // rounds are compile-time: 1 .. 4
                        // its grid is one workgroup per W_down tile: only a grid that fills the chip streams as fast as the GEMVs'
                        // (goldie, 96 tiles: 10.2 us against 4.6 + 4.0)
-                       (wfv == 2 || L0.down.ntiles * 4 >= e->num_cus * 3);
+                       (e->knobs.wide_ffn == 2 || L0.down.ntiles * 4 >= e->num_cus * 3);
             for (const auto &L : e->layers)
                 okw = okw && L.gate.wtype == L.qkv.wtype && L.up.wtype == L.qkv.wtype && L.down.wtype == L.qkv.wtype &&
                       (L.qkv.wtype == WT_Q8_0 || L.qkv.wtype == WT_Q4_0) &&
@@ -2839,8 +2929,7 @@ int nl_finalize(nl_handle e) {
             e->wide_ngc = (dgroups + 15) / 16 <= 1 ? 1 : 3;       // (two groups per wavefront run as three, the third masked)
             return okw && wide_ffn_lds_bytes(e->wide_nf, L0.down.npairs) <= (size_t)160 * 1024;
         };
-        const char *tf = getenv("NL_TP_FUSED");            // knob (tests, tools): 0 keeps a rank on the projection + attention plan
-        bool ok3 = want != 0 && want != 2 && !(tf && atoi(tf) == 0) && e->hd == 64 && e->G > 1 && c.n_layers < 127 &&
+        bool ok3 = want != 0 && want != 2 && e->knobs.tp_fused && e->hd == 64 && e->G > 1 && c.n_layers < 127 &&
                    ((e->p2p.on && !(c.flags & NL_FLAG_LOCAL_GROUP)) || group_fused);
         for (const auto &L : e->layers) {
             ok1 = ok1 && L.wo_head.ready && L.wo_head.wtype == L.qkv.wtype && (L.qkv.wtype == WT_Q8_0 || L.qkv.wtype == WT_Q4_0);
@@ -2884,13 +2973,11 @@ int nl_finalize(nl_handle e) {
             // workgroup per compute unit), else a gate + up tile pair each; EVERY block b < ceil(D / 16) owns W_down tile b
             const int ngroups = (L0.gate.npairs + KL - 1) / KL, dgroups = (L0.down.npairs + KL - 1) / KL;
             const int budget = e->num_cus - e->num_cus / 16;
-            const char *pk = getenv("NL_TP_PAIR");     // developer knob (tools/, tests)
-            t.pair = pk ? (atoi(pk) != 0) : (2 * L0.gate.ntiles > budget);
+            t.pair = e->knobs.tp_pair ? *e->knobs.tp_pair != 0 : 2 * L0.gate.ntiles > budget;
             t.n_prod = t.pair ? L0.gate.ntiles : 2 * L0.gate.ntiles;
             // W_down: blocks [0, n_cons) own ct tiles each (every consumer gathers all of h: fewer consumers = less fabric
             // traffic per gather, more tiles per consumer = more vector work per compute unit; 2 measured best at tp 8)
-            const char *ck = getenv("NL_TP_CT");      // developer knob (tools/)
-            int ct = ck ? atoi(ck) : (L0.down.npairs <= 24 ? 2 : 1);   // (tp 8 of the 7.9B tier: 2; tp 4: 1 -- measured, tools/r4_tp3.sh)
+            int ct = e->knobs.tp_ct.value_or(L0.down.npairs <= 24 ? 2 : 1);   // (tp 8 of the 7.9B tier: 2; tp 4: 1 -- measured, tools/r4_tp3.sh)
             if (ct != 1 && ct != 2 && ct != 4 && ct != 8 && ct != 16) ct = 2;
             while (ct > 1 && (dgroups + 16 / ct - 1) / (16 / ct) > 2) ct /= 2;
             t.ct_shift = ct == 1 ? 0 : ct == 2 ? 1 : ct == 4 ? 2 : ct == 8 ? 3 : 4;
@@ -2900,8 +2987,7 @@ int nl_finalize(nl_handle e) {
             t.ngc = (dgroups + 16 / ct - 1) / (16 / ct);
             t.nr = (L0.gate.ntiles * GPT + TP_THREADS - 1) / TP_THREADS;
             const bool tpffn = t.ngc <= 2 && t.nf <= 2 && t.nr <= 2 && t.n_prod <= budget && L0.down.npairs <= 128;
-            const char *tw = getenv("NL_TP_WIDE");               // developer knob: 1 = prefer wide_ffn_kernel wherever it is eligible
-            e->wide_ffn = ok3 && (!tpffn || (tw && atoi(tw) != 0)) && wide_ffn_ok();   // (a shard too large for one-tile producers: tp 2 of the 7.9B tier)
+            e->wide_ffn = ok3 && (!tpffn || e->knobs.tp_wide) && wide_ffn_ok();   // (a shard too large for one-tile producers: tp 2 of the 7.9B tier)
             ok3 = ok3 && (tpffn || e->wide_ffn);
             for (const auto &L : e->layers)   // (every layer has the shapes of layer 0: checked, not assumed)
                 ok3 = ok3 && L.wo.npairs == L0.wo.npairs && L.gate.ntiles == L0.gate.ntiles && L.down.npairs == L0.down.npairs &&
@@ -2916,8 +3002,7 @@ int nl_finalize(nl_handle e) {
         // grid has to be resident together (as in mode 2).  NL_ATTN_WO=0 keeps mode 2.
         bool ok4 = false;
         {
-            const char *aw = getenv("NL_ATTN_WO");
-            ok4 = ok2 && !ok1 && !ok3 && want != 2 && e->G == 1 && !e->p2p.on && !(aw && atoi(aw) == 0) && c.n_layers < 127 && e->grp_grid_fits;
+            ok4 = ok2 && !ok1 && !ok3 && want != 2 && e->G == 1 && !e->p2p.on && e->knobs.attn_wo && c.n_layers < 127 && e->grp_grid_fits;
             if (ok4) {
                 nl_engine::TpGeom &t = e->tpg;
                 const nl_engine::Layer &L0 = e->layers[0];
@@ -2940,7 +3025,6 @@ int nl_finalize(nl_handle e) {
         e->fused_mode = ok1 ? 1 : ok3 ? 3 : ok4 ? 4 : ok2 ? 2 : 0;
         e->fused = e->fused_mode != 0;
         if (e->fused_mode != 3) e->wide_ffn = e->fused_mode == 4 && wide_ffn_ok();     // the feed-forward half as one launch too
-        const char *fm = getenv("NL_FUSED_MAX_POS");
         // tools/fused_limit.py: the per-head blocks (mode 1) win up to ~500 (nano) / ~600 (mini) positions, the projection +
         // attention launch of the wide tiers (mode 2) up to ~390 (big)
         // (mode 4, tools/fused_limit.py on big, profiles/r04_big_fused_limit.log: with 256-position passes the two-launch layers
@@ -2949,23 +3033,21 @@ int nl_finalize(nl_handle e) {
         //  (mode 3 runs the same attention half: 512 = two of its passes, where 384 was three of the old 128-position ones)
         //  (round 5, the same tool with the feed-forward launch on the matrix pipe and its first round warm: 1.76 against 1.85 ms at
         //  position 800, 1.80 against 1.86 at 980 -- the two-launch layers now stay ahead through all four passes)
-        e->fused_max_pos = fm ? atoi(fm) : e->fused_mode == 4 ? (e->wide_ffn ? 1024 : 768) : (e->fused_mode == 1 || e->fused_mode == 3) ? 512 : 384;
+        e->fused_max_pos = e->knobs.fused_max_pos ? *e->knobs.fused_max_pos : e->fused_mode == 4 ? (e->wide_ffn ? 1024 : 768) : (e->fused_mode == 1 || e->fused_mode == 3) ? 512 : 384;
         {
             // long contexts on one GPU (mode 4): a head's 256-position passes are shared by its runner and three blocks that are not
             // runners -- two of its own kv group (members G .. 3G - 1) and one of the blocks past the kv groups (nl_tp.h) --, up to
             // two passes each: the two-launch layers then serve every position of the reference's context (2048, go/model.go:145-148)
             const int members = (e->gqa + 2) * 4 / e->grp_tpm, lgrid = grp_grid(e->KVs, members);
             const int grid4 = std::max(lgrid, (e->layers[0].wo.ntiles + e->tpg.wo_tpw - 1) / e->tpg.wo_tpw);
-            const char *hk = getenv("NL_ATTN_HELPERS");
-            e->attn_helpers = e->fused_mode == 4 && !(hk && atoi(hk) == 0) && !c.qk_norm && members - e->gqa >= 2 * e->gqa && grid4 - lgrid >= e->Hs &&
+            e->attn_helpers = e->fused_mode == 4 && e->knobs.attn_helpers && !c.qk_norm && members - e->gqa >= 2 * e->gqa && grid4 - lgrid >= e->Hs &&
                               e->layers[0].qkv.wtype == WT_Q4_0;      // (the Q8_0 variant of that launch does not fit 128 registers: 278 spilled)
-            if (!fm && e->attn_helpers && e->wide_ffn) e->fused_max_pos = 2 * TP_NCH_MAX * TP_PASS;
+            if (!e->knobs.fused_max_pos && e->attn_helpers && e->wide_ffn) e->fused_max_pos = 2 * TP_NCH_MAX * TP_PASS;
         }
         if (e->fused_mode == 3 || e->fused_mode == 4)      // passes a head takes inside the launch
             e->fused_max_pos = std::min(e->fused_max_pos, (e->attn_helpers ? 2 : 1) * TP_NCH_MAX * TP_PASS);
         {
-            const char *ff = getenv("NL_FUSED_FFN");   // knob (tests, tools): 0 keeps gate/up and down as two launches
-            bool okf = e->fused_mode == 1 && !(ff && atoi(ff) == 0);
+            bool okf = e->fused_mode == 1 && e->knobs.fused_ffn;
             for (const auto &L : e->layers)
                 okf = okf && L.dn_slice.ready && L.dn_slice.wtype == L.qkv.wtype && L.gate.wtype == L.qkv.wtype && L.up.wtype == L.qkv.wtype;
             e->ffn_fused = okf;
@@ -2997,11 +3079,10 @@ int nl_finalize(nl_handle e) {
             HIPCK(e, hipMemset(e->tp_hx, 0, nh * sizeof(u32x4)));
             // Q4_0 dot products of the two launches on the matrix pipe (nl_tp.h mf_*): matrices whose rows are whole 256-column
             // groups get the permuted second copy the quads of v_mfma_i32_4x4x4_16b_i8 need (+ their size in HBM)
-            const char *mk = getenv("NL_MFMA_DOT");          // knob (A/B, tests): 0 keeps the vector-pipe dot products
-            // (1, the default: the feed-forward launch only -- there a column group's digit image serves three rounds; in the attention
-            //  launch it serves one tile and the conversion eats the gain: 13.5 against 13.3 us, profiles/r05_big_kernel_times_variants.log;
-            //  2 switches that one on as well)
-            bool ma = mk && atoi(mk) == 2 && e->Hs % 4 == 0, mf = !(mk && atoi(mk) == 0) && e->wide_ffn;
+            // (NL_MFMA_DOT=1, the default: the feed-forward launch only -- there a column group's digit image serves three rounds; in the
+            //  attention launch it serves one tile and the conversion eats the gain: 13.5 against 13.3 us,
+            //  profiles/r05_big_kernel_times_variants.log; 2 switches that one on as well)
+            bool ma = e->knobs.mfma_dot == 2 && e->Hs % 4 == 0, mf = e->knobs.mfma_dot != 0 && e->wide_ffn;
             for (const auto &L : e->layers) {
                 ma = ma && L.qkv.wtype == WT_Q4_0 && L.qkv.npairs % KL == 0 && (L.qkv.npairs / KL) <= 16;
                 mf = mf && L.gate.wtype == WT_Q4_0 && L.up.wtype == WT_Q4_0 && L.down.wtype == WT_Q4_0 && L.gate.npairs % KL == 0 && L.down.npairs % KL == 0;
@@ -3025,7 +3106,7 @@ int nl_finalize(nl_handle e) {
             e->mf_attn = ma; e->mf_ffn = mf;
         }
     }
-    const bool has_coll = (e->G > 1 || e->force_tp_plan) && !e->p2p.on;
+    const bool has_coll = (e->G > 1 || e->knobs.force_tp_plan) && !e->p2p.on;
     if (has_coll && !e->comm && !(c.flags & NL_FLAG_LOCAL_GROUP))
         return e->fail(NL_ERR_STATE, "collective plan needs nl_comm_init before nl_finalize");
     HIPCK(e, hipStreamSynchronize(e->stream));
@@ -3087,12 +3168,7 @@ int nl_set_gamma(nl_handle e, const int32_t *indices, int n, const void *values,
     float *old_val = e->gamma_val;
     e->gamma_row = new_row;
     e->gamma_val = new_val;
-    for (auto &G : e->bt_graphs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); }
-    e->bt_graphs.clear();
-    for (auto &sb : e->sub) {   // the sub-batch step graphs hold the old tables too
-        for (auto &G : sb.graphs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); }
-        sb.graphs.clear();
-    }
+    destroy_step_graphs(e);   // (they hold the old tables too)
     if (e->finalized) {  // the launch closures hold the old pointers: rebuild plans and graphs
         destroy_samp_graphs(e);
         if (build_all(e)) {   // the rebuilt eager plans are valid; only the graphs were lost
@@ -3139,10 +3215,9 @@ int nl_destroy(nl_handle e) {
         for (void *p : bb) if (p) hipFree(p);
         if (b.h_meta) hipHostFree(b.h_meta);
     };
+    destroy_step_graphs(e);
     batch_free(e->bt);
-    for (auto &G : e->bt_graphs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); }
     for (auto &sb : e->sub) {
-        for (auto &G : sb.graphs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); }
         batch_free(sb.bt);
         if (sb.done) (void)hipEventDestroy(sb.done);
         if (sb.st) (void)hipStreamDestroy(sb.st);
@@ -3220,7 +3295,7 @@ int nl_forward(nl_handle e, int stream, int token, int pos, float *logits_out) {
     for (int attempt = 0;; attempt++) {
         if ((rc = note_positions(e, stream, pos, 1))) return rc;
         // one GPU: the LM head stores the logits into the pinned buffer itself (ctl[CTL_HOSTOUT]); groups: a DMA behind the step
-        const bool direct = logits_out && e->d_h_logits && e->G == 1 && !e->force_tp_plan && !e->p2p.on;
+        const bool direct = logits_out && e->d_h_logits && e->G == 1 && !e->knobs.force_tp_plan && !e->p2p.on;
         if ((direct || !logits_out) && call_step(e, token, pos, stream, direct ? 1 : 0, nullptr, &rc)) {
             if (rc) return rc;       // (the call box: no control copy, no synchronise; the logits rows are in the pinned buffer)
         } else {
@@ -3335,12 +3410,12 @@ int nl_decode_greedy(nl_handle e, int stream, int token, int pos, int n_steps, i
 namespace {
 
 // ---- on-device sampling ----------------------------------------------------
-// lane chunk of the select kernel: a multiple of 32 covering vocab / 1024 (vocab <= 131072)
+// lane chunk of the select kernel: a multiple of 32 covering vocab / 1024 (vocab <= 2^17)
 inline int samp_chunk(int vocab) { return ((vocab + SAMP_THREADS - 1) / SAMP_THREADS + 31) / 32 * 32; }
 
 hipError_t samp_alloc(SampScratch &s, int vocab, int n_uniforms) {
     hipError_t rc;
-    if (samp_chunk(vocab) > 128) return hipErrorInvalidValue;   // vocab > 131072
+    if (samp_chunk(vocab) > 128) return hipErrorInvalidValue;   // vocab > 2^17
     const int nblocks = (vocab + 255) / 256;
 #define SA(ptr, count) if ((rc = hipMalloc((void **)&(ptr), (size_t)(count) * 4)) != hipSuccess) return rc
     SA(s.keys_in, SAMP_THREADS * samp_chunk(vocab));   // (whole lane chunks: the select kernels load past vocab and mask)
@@ -3370,7 +3445,7 @@ hipError_t launch_sample(const SampScratch &s, float *logits, int vocab, const n
     P.scal = s.scal; P.pmax = s.pmax; P.nblocks = (vocab + 255) / 256;
     P.h1g = s.h1g; P.nblocks_pen = P.nblocks;
     // Three selections, none with a sort (nl_sample.h): temp <= 0 -> argmax of the penalised logits; top_p < 1 -> sampleTopP by
-    // weighted radix selection (<= 32768 candidates in the registers of the one workgroup, up to 131072 streamed out of L2);
+    // weighted radix selection (<= 32768 candidates in the registers of the one workgroup, up to 2^17 streamed out of L2);
     // otherwise sampleTopK by a 2-bit-per-pass selection of the k-th largest logit + a bitonic network over the <= 1024 candidates
     P.radix = p.temperature > 0.f && p.top_p < 1.0f ? 1 : 0;
     hipLaunchKernelGGL(samp_penalty_kernel, dim3(P.nblocks), dim3(256), 0, st, P);
@@ -3468,7 +3543,7 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
                 int rc2 = NL_OK;
                 // one GPU: the launch that picks the token also fetches its embedding row, and the plan's own embed and
                 // argmax launches (the argmax of logits nobody reads) are left out of the graph -- two launches per token
-                const bool tail = e->G == 1 && !e->p2p.on && !e->force_tp_plan && !getenv("NL_NO_SAMPLE_EMBED");
+                const bool tail = e->G == 1 && !e->p2p.on && !e->knobs.force_tp_plan && e->knobs.sample_embed;
                 for (int q = 0; cs == hipSuccess && q < e->graph_steps && !rc2; q++) {
                     if (launch_sample(s, e->logits, e->cfg.vocab, *p, e->ctl, e->ids, e->stream, tail ? &e->plan_embed : nullptr) != hipSuccess) rc2 = NL_ERR_HIP;
                     else if (!tail) rc2 = run_plan_eager(e, e->ps[k]);
@@ -3561,9 +3636,10 @@ int nl_prefill(nl_handle e, int stream, const int *tokens, int n, int pos0, floa
     HIPCK(e, hipSetDevice(e->dev));
     if (int qrc = pd_session_close(e)) return qrc;
     if ((rc = note_positions(e, stream, pos0, n))) return rc;
-    if (n >= NL_BATCH_MIN && batch_supported(e)) {
+    const StepKnobs k;
+    if (n >= process_knobs().batch_min && batch_supported(e)) {
         // multi-token path: 64-token tiles on the matrix cores; causality comes from each token's own pos
-        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e))) return rc; }
+        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc; }
         nl_engine::Batch &b = e->bt;
         for (int t0 = 0; t0 < n; t0 += b.cap) {
             const int m = std::min(b.cap, n - t0);
@@ -3574,7 +3650,7 @@ int nl_prefill(nl_handle e, int stream, const int *tokens, int n, int pos0, floa
                 b.h_meta[2 * b.cap + i] = stream;
             }
             const bool last = t0 + m == n;
-            if ((rc = batched_step(e, b, e->stream, m, last ? 2 : 0, true))) return rc;
+            if ((rc = batched_step(e, b, e->stream, m, last ? 2 : 0, k, true))) return rc;
             if (last) {
                 // keep the single-token state coherent: logits / argmax of the last token
                 HIPCK(e, hipMemcpyAsync(e->logits, b.logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
@@ -3624,70 +3700,29 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
     if (int qrc = pd_session_close(e)) return qrc;
     for (int i = 0; i < n; i++)
         if ((rc = note_positions(e, streams[i], pos[i], 1))) return rc;
-    if (n >= NL_BATCH_MIN && batch_supported(e)) {
+    const StepKnobs k;
+    if (n >= process_knobs().batch_min && batch_supported(e)) {
         // The streams of a batch are independent: cut it into groups of >= 16 that step concurrently, each on its own HIP
         // stream with its own step buffers, so that one dependent chain's launch heads and memory round trips overlap
         // another's work (a 64-stream step of the 841M tier is ~224 launches of <= 144 workgroups on a 256-CU chip).  The
         // arithmetic per stream does not depend on the group it steps in: results are bitwise those of the one-step form.
         // (off unless NL_SUB_BATCHES > 1 -- measured slower, profiles/r04_subbatch_groups.log: the default is the chunked loop below)
-        const int groups = e->sub_batches > 1 ? std::max((n + QG_TOK - 1) / QG_TOK, std::min(e->sub_batches, n / 16)) : 1;
-        // (a step's launch list and kernel arguments also depend on the test knobs batched_step reads per step: all of them are
-        //  part of the key of a cached step graph)
-        auto batch_knob_sig = [] {
-            const char *rk = getenv("NL_ROPE_IN_ATTN"), *fk = getenv("NL_FOLD_NORM"), *pk = getenv("NL_PREFILL_PRECISION"), *kk = getenv("NL_KV16_MIN_TOKENS"),
-                       *dk = getenv("NL_DGEMM"), *dm = getenv("NL_DGEMM_MAX_TOKENS"), *hk = getenv("NL_DGEMM_HEAD");
-            return 40503 * (hk ? atoi(hk) + 1 : 0) + (rk ? atoi(rk) + 1 : 0) + 3 * (fk ? atoi(fk) + 1 : 0) + 9 * (pk && !strcmp(pk, "fp16x1") ? 1 : 0) +
-                   18 * (dk ? atoi(dk) + 1 : 0) + 54 * (dm ? (atoi(dm) & 0xff) + 1 : 0) + 13878 * (kk ? (atoi(kk) & 0xfff) + 1 : 0);
-        };
+        const int groups = e->knobs.sub_batches > 1 ? std::max((n + QG_TOK - 1) / QG_TOK, std::min(e->knobs.sub_batches, n / 16)) : 1;
         if (groups > 1 && groups <= 4) {
             if (!e->sub_fork) HIPCK(e, hipEventCreateWithFlags(&e->sub_fork, hipEventDisableTiming));
             HIPCK(e, hipEventRecord(e->sub_fork, e->stream));      // (the position bookkeeping above may have queued row clears)
             const int per = (n + groups - 1) / groups;
-            // (a step's launch list and kernel arguments also depend on the test knobs batched_step reads per step: all of them
-            //  are part of the key of a cached step graph)
-            const int knob_sig = batch_knob_sig();
             for (int g = 0, t0 = 0; g < groups; g++, t0 += per) {
                 const int m = std::min(per, n - t0);
                 if (m <= 0) break;
                 nl_engine::SubBatch &sb = e->sub[g];
-                { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, sb.bt, QG_TOK)) || (rc = dgemm_prepare(e))) return rc; }
+                { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, sb.bt, QG_TOK)) || (rc = dgemm_prepare(e, k))) return rc; }
                 if (!sb.st) {
                     HIPCK(e, hipStreamCreateWithFlags(&sb.st, hipStreamNonBlocking));
                     HIPCK(e, hipEventCreateWithFlags(&sb.done, hipEventDisableTiming));
                 }
-                nl_engine::Batch &b = sb.bt;
-                int nsplit = 1;
-                for (int i = 0; i < m; i++) {
-                    b.h_meta[i] = tokens[t0 + i];
-                    b.h_meta[b.cap + i] = pos[t0 + i];
-                    b.h_meta[2 * b.cap + i] = streams[t0 + i];
-                    nsplit = std::max(nsplit, pos[t0 + i] / ATT_CH + 1);
-                }
-                const int key_split = nsplit * 131072 + knob_sig;
                 HIPCK(e, hipStreamWaitEvent(sb.st, e->sub_fork, 0));
-                hipGraphExec_t exec = nullptr;
-                for (auto &G : sb.graphs)
-                    if (G.n == m && G.nsplit == key_split) exec = G.exec;
-                if (!exec && e->use_graph) {
-                    // the step reads its tokens / positions / streams from the pinned block behind h_meta (a copy node of the
-                    // graph), so one graph serves every step of m streams with as many position splits
-                    std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
-                    hipGraph_t gr = nullptr;
-                    if (hipStreamBeginCapture(sb.st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                        const int rc2 = batched_step(e, b, sb.st, m, 1);
-                        const hipError_t ce = hipStreamEndCapture(sb.st, &gr);
-                        if (!rc2 && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess) {
-                            sb.graphs.push_back({m, key_split, gr, exec});
-                        } else {
-                            if (gr) (void)hipGraphDestroy(gr);
-                            (void)hipGetLastError();
-                            exec = nullptr;
-                        }
-                    }
-                    (void)hipGetLastError();
-                }
-                if (exec) HIPCK(e, hipGraphLaunch(exec, sb.st));
-                else if ((rc = batched_step(e, b, sb.st, m, 1))) return rc;
+                if ((rc = decode_step(e, sb.bt, sb.graphs, sb.st, streams + t0, tokens + t0, pos + t0, m, k))) return rc;
                 HIPCK(e, hipEventRecord(sb.done, sb.st));
                 HIPCK(e, hipStreamWaitEvent(e->stream, sb.done, 0));     // later work on the engine's stream follows every group
             }
@@ -3707,44 +3742,12 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
             HIPCK(e, hipStreamSynchronize(e->stream));
             return NL_OK;
         }
-        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e))) return rc; }
+        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc; }
         nl_engine::Batch &b = e->bt;
         for (int t0 = 0; t0 < n; t0 += b.lm_cap) {
             const int m = std::min(b.lm_cap, n - t0);
-            HIPCK(e, hipStreamSynchronize(e->stream));
-            for (int i = 0; i < m; i++) {
-                b.h_meta[i] = tokens[t0 + i];
-                b.h_meta[b.cap + i] = pos[t0 + i];
-                b.h_meta[2 * b.cap + i] = streams[t0 + i];
-            }
-            // The step as one hipGraph, cached by (streams, position splits, knobs): it reads its tokens / positions / streams from
-            // the pinned block behind h_meta (a copy node of the graph), so one graph serves every step of that geometry.  The 150+
-            // launches of a step are 3 us each when a host thread queues them one by one -- more than the kernels of a decode batch.
-            hipGraphExec_t exec = nullptr;
-            if (e->use_graph) {
-                int nsplit = 1;
-                for (int i = 0; i < m; i++) nsplit = std::max(nsplit, pos[t0 + i] / ATT_CH + 1);
-                const int key_split = nsplit * 131072 + batch_knob_sig() % 131072;
-                for (auto &G : e->bt_graphs)
-                    if (G.n == m && G.nsplit == key_split) exec = G.exec;
-                if (!exec) {
-                    std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
-                    hipGraph_t gr = nullptr;
-                    if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                        const int rc2 = batched_step(e, b, e->stream, m, 1);
-                        const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
-                        if (!rc2 && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess) {
-                            e->bt_graphs.push_back({m, key_split, gr, exec});
-                        } else {
-                            if (gr) (void)hipGraphDestroy(gr);
-                            exec = nullptr;
-                        }
-                    }
-                    (void)hipGetLastError();
-                }
-            }
-            if (exec) HIPCK(e, hipGraphLaunch(exec, e->stream));
-            else if ((rc = batched_step(e, b, e->stream, m, 1))) return rc;
+            HIPCK(e, hipStreamSynchronize(e->stream));     // (h_meta is reused per chunk)
+            if ((rc = decode_step(e, b, e->bt_graphs, e->stream, streams + t0, tokens + t0, pos + t0, m, k))) return rc;
             if (logits_out)
                 HIPCK(e, hipMemcpyAsync(logits_out + (size_t)t0 * e->cfg.vocab, b.logits, (size_t)m * e->cfg.vocab * 4,
                                         hipMemcpyDeviceToHost, e->stream));
@@ -3976,8 +3979,6 @@ int nl_op_matmul(int device, uint32_t type, const void *w, uint64_t nbytes, cons
         if (repack(&tmp, m, d_raw, (int)type, cols, 0, rows, 0, cols, 0, m.ntiles, ROWMAP_IDENT) != hipSuccess) break;
         GemvParams P{};
         P.q0 = m.q; P.s0 = m.s; P.rows = rows; P.cols = cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
-        if (const char *v = getenv("NL_TW")) tmp.tw_override = atoi(v);
-        if (const char *v = getenv("NL_KW")) tmp.kw_override = atoi(v);
         choose_geometry(&tmp, m, P.tw, P.kw);
         P.x = d_x; P.out = d_out;
         if (launch_gemv_t<PRO_PLAIN, EPI_STORE>(m.wtype, P, st) != hipSuccess) break;
@@ -4026,7 +4027,7 @@ int nl_op_matmul_batch(int device, uint32_t type, const void *w, uint64_t nbytes
         if (hipMalloc((void **)&d_xf, xfrag_uint4(cols, n_tokens) * sizeof(uint4)) != hipSuccess) break;
         if (launch_xsplit(m.wtype, d_x, cols, cols, n_tokens, d_xf, st) != hipSuccess) break;
         P.xf = d_xf; P.n_tokens = n_tokens; P.out = d_out; P.ldo = rows;
-        if (launch_qgemm(m.wtype, P, st) != hipSuccess) break;
+        if (launch_qgemm(m.wtype, P, StepKnobs{}, st) != hipSuccess) break;
         if (hipMemcpyAsync(out, d_out, (size_t)rows * n_tokens * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
         if (hipStreamSynchronize(st) != hipSuccess) break;
         rc = NL_OK;
@@ -4216,7 +4217,7 @@ int nl_comm_init(nl_handle e, const void *id) {
     if (e && e->grp) return e->fail(NL_ERR_UNSUPPORTED, "nl_comm_init on a device group: nl_create_group wires its ranks itself");
     if (!e || !id) return NL_ERR_INVALID;
     if (e->finalized) return e->fail(NL_ERR_STATE, "nl_comm_init after nl_finalize");
-    if (e->G <= 1 && !e->force_tp_plan) return NL_OK;
+    if (e->G <= 1 && !e->knobs.force_tp_plan) return NL_OK;
     std::string err;
     if (!g_rccl.load(err)) return e->fail(NL_ERR_COMM, "%s", err.c_str());
     HIPCK(e, hipSetDevice(e->dev));
@@ -4245,20 +4246,18 @@ int p2p_alloc_area(nl_engine *e) {
         // silently.  So there is no cached fallback: without an uncached, exportable allocation the push path is
         // refused and the caller (bench.py, load_llama_model) falls back to RCCL.  NL_P2P_CACHED=1 is a test knob for
         // ranks that share ONE device (one L2, nothing to shadow); it is rejected across devices at import.
-        const bool test_cached = getenv("NL_P2P_CACHED") != nullptr;
-        hipError_t s = test_cached ? hipMalloc(&p.area, p.bytes) : hipExtMallocWithFlags(&p.area, p.bytes, hipDeviceMallocUncached);
+        hipError_t s = e->knobs.p2p_cached ? hipMalloc(&p.area, p.bytes) : hipExtMallocWithFlags(&p.area, p.bytes, hipDeviceMallocUncached);
         if (s != hipSuccess) {
             (void)hipGetLastError();
             p.area = nullptr;
             return e->fail(NL_ERR_UNSUPPORTED, "push all-reduce needs an uncached receive area (hipExtMallocWithFlags: %s); use RCCL", hipGetErrorString(s));
         }
-        p.uncached = !test_cached;
+        p.uncached = !e->knobs.p2p_cached;
         HIPCK(e, hipMemset(p.area, 0, p.bytes));
         HIPCK(e, hipMalloc((void **)&p.epoch, 2 * sizeof(unsigned)));
         HIPCK(e, hipMemset(p.epoch, 0, 2 * sizeof(unsigned)));
         p.status = p.epoch + 1;
-        const char *tm = getenv("NL_P2P_TIMEOUT_MS");
-        p.timeout_ticks = (long long)(tm ? atoi(tm) : 10000) * 100000;   // wall_clock64: 100 MHz
+        p.timeout_ticks = (long long)e->knobs.p2p_timeout_ms * 100000;   // wall_clock64: 100 MHz
         e->bytes_state += p.bytes;
     }
     return NL_OK;

@@ -226,3 +226,34 @@ def test_models_outside_dgemm_keep_the_split_k_launches(hip, tmp_path):
         ids, _ = dev.forward_batch(list(range(8)), [5] * 8, [0] * 8)
         assert len(ids) == 8 and dev.memory_usage()["weights"] == w0, shape.name
         dev.close()
+
+
+def test_step_graph_is_not_replayed_under_other_knobs(hip, tmp_path, monkeypatch):
+    # A decode batch's step is a cached hipGraph keyed on the step knobs.  50 streams (one chunk: lm_cap = 64) under
+    # NL_DGEMM_MAX_TOKENS=300 capture a graph of dgemm launches; the next step under 44 must be the split-K launches, bitwise those
+    # of a fresh handle that only ran under 44 -- not a replay of the dgemm graph (300 and 44 agree in their low byte).  Every step
+    # is at position 0, so no step reads K / V rows an earlier one wrote.
+    shape = SHAPES["k256_i768_bias"]
+    p = tmp_path / "m.gguf"
+    synth.generate_gguf(str(p), shape, "q4_0", 211)
+    g = gguf.load_gguf(str(p))
+    ns = 50
+    toks = [int(t) for t in np.random.Generator(np.random.PCG64(19)).integers(3, shape.vocab, size=ns)]
+
+    def step(dev):
+        _, lg = dev.forward_batch(list(range(ns)), toks, [0] * ns, want_logits=True)
+        return lg.copy()
+
+    monkeypatch.setenv("NL_DGEMM_MAX_TOKENS", "300")
+    dev = hip.load_llama_model(g, max_streams=ns)
+    on_dgemm = step(dev)
+    monkeypatch.setenv("NL_DGEMM_MAX_TOKENS", "44")
+    after = step(dev)
+    dev.close()
+    fresh = hip.load_llama_model(g, max_streams=ns)
+    want = step(fresh)
+    fresh.close()
+    monkeypatch.delenv("NL_DGEMM_MAX_TOKENS")
+    assert on_dgemm.tobytes() != want.tobytes()          # the two paths differ in bits here: the check below can tell them apart
+    assert float(np.abs(on_dgemm - want).max()) <= 2e-5 * max(1.0, float(want.std()))
+    assert after.tobytes() == want.tobytes()

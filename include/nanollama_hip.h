@@ -163,6 +163,18 @@ NL_API int nl_prefill(nl_handle h, int stream, const int *tokens, int n, int pos
  * stream's greedy argmax.  Streams must be distinct. */
 NL_API int nl_forward_batch(nl_handle h, const int *streams, const int *tokens, const int *pos, int n,
                             float *logits_out, int *next_ids);
+/* One decode step of n concurrent streams followed, for each of them, by the sampling half of Engine.Generate's loop
+ * (go/main.go:177-200) with that stream's own settings, on the device: for i < n, Forward(tokens[i], pos[i]) on stream
+ * streams[i]; repetition penalty over its recent window (recent + i * recent_stride, n_recent[i] ids, oldest first;
+ * :177-187); sampleTopP when params[i].top_p < 1, else sampleTopK (temperature <= 0: argmax; :191-195, :294-408) with
+ * uniforms[i] as e.rng.Float32(); the pick appended to the window (:197-200, in/out) and returned in next_ids[i].
+ * No logits leave the device.  n <= 64 and <= max_streams, streams distinct, every params[i] as nl_sample_decode takes it,
+ * recent_stride >= every rep_window, n_recent[i] <= rep_window; vocabularies above 131072 and device groups return
+ * NL_ERR_UNSUPPORTED.  A row's id is bitwise what the host sampler picks from the logits nl_forward_batch returns for the
+ * same call; nothing but KV rows and position marks outlives the call. */
+NL_API int nl_forward_batch_sample(nl_handle h, const int *streams, const int *tokens, const int *pos, int n,
+                                   const nl_sample_params *params, const float *uniforms,
+                                   int *recent, int recent_stride, int *n_recent, int *next_ids);
 
 /* == introspection / measurement ========================================== */
 NL_API int nl_get_config(nl_handle h, nl_config *out); /* effective config (after seq_len cap etc.) */

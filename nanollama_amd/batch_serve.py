@@ -1,0 +1,192 @@
+"""Continuous batching behind POST /chat: concurrent requests decode as one sampled batch (nl_forward_batch_sample).
+
+The reference serves one request at a time (go/serve.go:56,106-108: one CPU engine behind a mutex).  Here one worker
+thread owns the model handle (single-caller) and runs a loop of steps; every step
+
+  1. admits waiting requests while a stream is free: reset(stream), prefill of the first n_prompt - 1 prompt tokens
+     (n_prompt = min(len, seq_len - 1), as Engine.generate_ids); the request joins with its last prompt token at
+     position n_prompt - 1;
+  2. steps every active request with one forward_batch_sample call -- Forward, penalty, sampling and the recent window of
+     every row on the device -- and applies the stop rules of Engine.generate_ids per row: EOS ends the request and is
+     not emitted (go/main.go:203); otherwise the id is emitted, and the output cap, max_tokens and the end of the context
+     each end the request.
+
+A finished request gets its text and frees its stream; a request that arrives meanwhile joins at the next step.  Settings
+per request follow go/serve.go:94-103 (temperature, max_tokens and top_k come from the request when > 0); top_p,
+rep_penalty and rep_window are the server's.  Each request samples from its own generator, seeded from the scheduler's
+(seeded by --seed) in admission order, and draws a uniform only while its temperature is > 0, as Engine does.
+"""
+from __future__ import annotations
+
+import collections
+import threading
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+
+from .engine import GenParams
+from .engine_text import TextOutput
+
+MAX_PARALLEL = 64            # rows of one nl_forward_batch_sample call (the LM head's batch)
+MAX_VOCAB = 131072           # the device sampler's vocabularies
+MAX_TOP_K = 1024             # the device sampler's top-k list
+
+
+class RequestError(Exception):
+    """A request the scheduler could not serve: status 400 (settings the device sampler does not take) or 500 (engine)."""
+
+    def __init__(self, status: int, message: str):
+        super().__init__(message)
+        self.status = status
+
+
+@dataclass
+class _Request:
+    tokens: List[int]
+    params: GenParams
+    done: threading.Event = field(default_factory=threading.Event)
+    text: str = ""
+    error: Optional[RequestError] = None
+
+
+@dataclass
+class _Row:
+    req: _Request
+    stream: int
+    token: int               # fed at `pos` by the next step
+    pos: int
+    rng: np.random.Generator
+    out: TextOutput
+    recent: List[int] = field(default_factory=list)
+    n_out: int = 0           # ids sampled so far (EOS included)
+
+
+class BatchScheduler:
+    def __init__(self, model, tokenizer, parallel: int, rep_penalty: float = 1.15, rep_window: int = 64,
+                 seed: Optional[int] = None):
+        if not 1 <= parallel <= min(MAX_PARALLEL, model.max_streams):
+            raise ValueError(f"parallel must be in [1, {min(MAX_PARALLEL, model.max_streams)}] (the handle's max_streams)")
+        if model.config.vocab_size > MAX_VOCAB:
+            raise ValueError(f"batched sampling covers vocabularies up to {MAX_VOCAB}, not {model.config.vocab_size}")
+        if not 0 <= rep_window <= 1024:
+            raise ValueError("rep_window must be in [0, 1024] for batched sampling")
+        self.model, self.tokenizer = model, tokenizer
+        self.parallel = parallel
+        self.eos_id = tokenizer.eos_id
+        self.rep_penalty = float(np.float32(rep_penalty))
+        self.rep_window = int(rep_window)
+        self.rng = np.random.default_rng(seed)
+        self.steps = 0                                  # forward_batch_sample calls so far
+        self._cv = threading.Condition()
+        self._queue: collections.deque = collections.deque()
+        self._closed = False
+        self._worker = threading.Thread(target=self._run, name="batch-scheduler", daemon=True)
+        self._worker.start()
+
+    # ---- callers (any thread) ----
+    def generate_quiet(self, prompt: str, params: GenParams) -> str:
+        """GenerateQuiet (go/main.go:233-291) as one row of the shared batch; blocks until the request is done.
+        Raises RequestError (status 400 / 500)."""
+        if not params.top_p > 0:
+            raise RequestError(400, f"top_p must be > 0, got {params.top_p}")
+        if params.temperature > 0 and params.top_p >= 1.0 and not 1 <= params.top_k <= MAX_TOP_K:
+            raise RequestError(400, f"top_k must be in [1, {MAX_TOP_K}] for batched sampling, got {params.top_k}")
+        req = _Request(self.tokenizer.encode(prompt, True), params)
+        with self._cv:
+            if self._closed:
+                raise RequestError(500, "scheduler closed")
+            self._queue.append(req)
+            self._cv.notify()
+        req.done.wait()
+        if req.error is not None:
+            raise req.error
+        return req.text
+
+    def close(self) -> None:
+        with self._cv:
+            self._closed = True
+            self._cv.notify()
+        self._worker.join()
+
+    # ---- the worker ----
+    def _finish(self, row: _Row, free: List[int]) -> None:
+        row.req.text = row.out.text()
+        free.append(row.stream)
+        row.req.done.set()
+
+    def _fail(self, req: _Request, status: int, exc: BaseException) -> None:
+        req.error = RequestError(status, f"{type(exc).__name__}: {exc}")
+        req.done.set()
+
+    def _admit(self, req: _Request, stream: int, active: List[_Row], free: List[int]) -> None:
+        cfg = self.model.config
+        p = req.params
+        rng = np.random.default_rng(int(self.rng.integers(0, 2 ** 63 - 1)))
+        n_prompt = min(len(req.tokens), max(cfg.seq_len - 1, 0))
+        row = _Row(req, stream, req.tokens[n_prompt - 1] if n_prompt else 0, n_prompt - 1, rng, TextOutput(self.tokenizer))
+        if p.max_tokens <= 0 or n_prompt <= 0:       # nothing to sample
+            self._finish(row, free)
+            return
+        try:
+            self.model.reset(stream)
+            if n_prompt > 1:
+                self.model.prefill(req.tokens[:n_prompt - 1], pos0=0, stream=stream, want_logits=False)
+        except Exception as exc:                        # engine error: this request fails, the scheduler goes on
+            free.append(stream)
+            self._fail(req, 500, exc)
+            return
+        active.append(row)
+
+    def _step(self, active: List[_Row], free: List[int]) -> None:
+        seq_len = self.model.config.seq_len
+        params = [dict(temperature=r.req.params.temperature, top_p=r.req.params.top_p, top_k=max(r.req.params.top_k, 1),
+                       rep_penalty=self.rep_penalty, rep_window=self.rep_window) for r in active]
+        uniforms = [r.rng.random(dtype=np.float32) if r.req.params.temperature > 0 else np.float32(0) for r in active]
+        try:
+            ids, recents = self.model.forward_batch_sample([r.stream for r in active], [r.token for r in active],
+                                                           [r.pos for r in active], params, uniforms,
+                                                           [r.recent for r in active])
+        except Exception as exc:                        # engine error: the requests of this call fail, the scheduler goes on
+            for r in active:
+                free.append(r.stream)
+                self._fail(r.req, 500, exc)
+            active.clear()
+            return
+        self.steps += 1
+        keep = []
+        for r, t, rec in zip(active, ids, recents):
+            r.recent, r.n_out = rec, r.n_out + 1
+            if t == self.eos_id:                        # go/main.go:203: not emitted
+                self._finish(r, free)
+                continue
+            capped = r.out.add(t)
+            r.token, r.pos = t, r.pos + 1
+            # Engine.generate_ids forwards the id at r.pos and stops when that leaves no position to sample from
+            # (pos + 1 >= seq_len after its increment), after max_tokens ids, or at the output cap
+            if capped or r.n_out >= r.req.params.max_tokens or r.pos + 1 >= seq_len:
+                self._finish(r, free)
+            else:
+                keep.append(r)
+        active[:] = keep
+
+    def _run(self) -> None:
+        free = list(range(self.parallel))
+        active: List[_Row] = []
+        while True:
+            with self._cv:
+                while not self._closed and not self._queue and not active:
+                    self._cv.wait()
+                if self._closed:
+                    pending = list(self._queue) + [r.req for r in active]
+                    self._queue.clear()
+                    break
+                admit = []
+                while self._queue and free:
+                    admit.append((self._queue.popleft(), free.pop(0)))
+            for req, stream in admit:
+                self._admit(req, stream, active, free)
+            if active:
+                self._step(active, free)
+        for req in pending:
+            self._fail(req, 500, RuntimeError("scheduler closed"))

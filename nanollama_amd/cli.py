@@ -37,7 +37,24 @@ def build_parser() -> argparse.ArgumentParser:
                     help="shard the model tensor-parallel over this many GPUs of the node (2, 4 or 8: devices --device .. --device + N - 1; "
                          "the 7.9B tier's configuration).  One process, one engine: --serve and --interactive work unchanged")
     ap.add_argument("--seed", type=int, default=None, help="sampling seed (default: entropy, like the reference)")
+    ap.add_argument("--parallel", type=int, default=1,
+                    help="with --serve: decode up to N concurrent /chat requests as one sampled batch (N <= 64; "
+                         "1 = one request at a time, as the reference)")
     return ap
+
+
+def check_parallel(args) -> None:
+    """--parallel: 1 is the serial server; N > 1 needs one GPU (a device group has no batched sampler)."""
+    if not 1 <= args.parallel <= 64:
+        raise RuntimeError("--parallel must be in [1, 64]")
+    if args.parallel > 1 and args.gpus > 1:
+        raise RuntimeError("--parallel > 1 needs --gpus 1")
+    if args.parallel > 1 and not 0 <= args.rep_window <= 1024:
+        raise RuntimeError("--parallel > 1 needs --rep-window <= 1024")
+
+
+def batched(args) -> bool:
+    return bool(args.serve) and args.parallel > 1
 
 
 def estimate_params(cfg) -> int:
@@ -67,7 +84,9 @@ def load_engine(args) -> TextEngine:
         print(f"[nanollama] tensor-parallel over devices {devs} (push all-reduce between the ranks of this process)")
         model = load_llama_model(g, devices=devs, verbose=True)
     else:
-        model = load_llama_model(g, device=args.device, verbose=True)
+        model = load_llama_model(g, device=args.device, max_streams=args.parallel if batched(args) else 1, verbose=True)
+    if batched(args) and model.config.vocab_size > 131072:
+        raise RuntimeError(f"--parallel > 1 covers vocabularies up to 131072, not {model.config.vocab_size}")
     if args.gamma:
         from .gamma import load_gamma
         try:
@@ -119,6 +138,7 @@ def main(argv=None) -> int:
         if args.list_tensors:
             list_tensors(load_gguf(args.model, verbose=True))
             return 0
+        check_parallel(args)
         eng = load_engine(args)
     except (GGUFError, OSError, RuntimeError, ImportError) as exc:
         print(f"error: {exc}", file=sys.stderr)
@@ -126,6 +146,16 @@ def main(argv=None) -> int:
     params = GenParams(max_tokens=args.max_tokens, temperature=args.temp, top_p=args.top_p, top_k=args.top_k)
     if args.serve:
         from .serve import run_server
+        if batched(args):
+            from .batch_serve import BatchScheduler
+            sched = BatchScheduler(eng.model, eng.tokenizer, args.parallel, rep_penalty=args.rep_penalty,
+                                   rep_window=args.rep_window, seed=args.seed)
+            print(f"[nanollama] continuous batching: up to {args.parallel} requests per decode step")
+            try:
+                run_server(sched, params, args.port)
+            finally:
+                sched.close()
+            return 0
         run_server(eng, params, args.port)
     elif args.interactive:
         run_repl(eng, params)

@@ -352,6 +352,12 @@ struct nl_engine {
     std::vector<StepGraph> bt_graphs;   // step graphs of the whole-batch decode step (bt), same key
     hipEvent_t sub_fork = nullptr;
 
+    // sampled decode batches (nl_forward_batch_sample): the 64-row sampler's scratch, the call's block (settings | uniforms |
+    // window lengths | ids | windows, bs_layout) in pinned and device memory, and step + sampler graphs keyed like bt_graphs
+    SampScratch bs;
+    int *bs_dev = nullptr, *h_bs = nullptr;
+    std::vector<StepGraph> bs_graphs;
+
     // on-device sampling (nl_sample_decode): scratch for one vocabulary, allocated on first use
     SampScratch sp;
     bool sp_ready = false;
@@ -2348,6 +2354,7 @@ int decode_step(nl_engine *e, nl_engine::Batch &b, std::vector<nl_engine::StepGr
 void destroy_step_graphs(nl_engine *e) {
     auto drop = [](std::vector<nl_engine::StepGraph> &gs) { for (auto &G : gs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); } gs.clear(); };
     drop(e->bt_graphs);
+    drop(e->bs_graphs);
     for (auto &sb : e->sub) drop(sb.graphs);
 }
 
@@ -3196,6 +3203,9 @@ int nl_destroy(nl_handle e) {
     pd_session_record(e, false);
     hipDeviceSynchronize();
     samp_free(e->sp);
+    samp_free(e->bs);
+    if (e->bs_dev) hipFree(e->bs_dev);
+    if (e->h_bs) hipHostFree(e->h_bs);
     for (auto &S : e->ps) destroy_graphs(S);
     destroy_samp_graphs(e);
     for (auto &L : e->layers) {
@@ -3413,53 +3423,77 @@ namespace {
 // lane chunk of the select kernel: a multiple of 32 covering vocab / 1024 (vocab <= 2^17)
 inline int samp_chunk(int vocab) { return ((vocab + SAMP_THREADS - 1) / SAMP_THREADS + 31) / 32 * 32; }
 
-hipError_t samp_alloc(SampScratch &s, int vocab, int n_uniforms) {
+// scratch of a `rows`-row sampler: keys_in, pmax and h1g are per-row slabs (acct: device bytes are counted there)
+hipError_t samp_alloc(SampScratch &s, int vocab, int n_uniforms, int rows = 1, size_t *acct = nullptr) {
     hipError_t rc;
     if (samp_chunk(vocab) > 128) return hipErrorInvalidValue;   // vocab > 2^17
     const int nblocks = (vocab + 255) / 256;
-#define SA(ptr, count) if ((rc = hipMalloc((void **)&(ptr), (size_t)(count) * 4)) != hipSuccess) return rc
-    SA(s.keys_in, SAMP_THREADS * samp_chunk(vocab));   // (whole lane chunks: the select kernels load past vocab and mask)
-    if ((rc = hipMemset(s.keys_in, 0, (size_t)SAMP_THREADS * samp_chunk(vocab) * 4)) != hipSuccess) return rc;
-    SA(s.scal, 4); SA(s.pmax, nblocks); SA(s.h1g, 2 * 2048);
-    if ((rc = hipMemset(s.h1g, 0, 2048 * 8)) != hipSuccess) return rc;
+    const size_t keys = (size_t)SAMP_THREADS * samp_chunk(vocab);   // (whole lane chunks: the select kernels load past vocab and mask)
+#define SA(ptr, count) if ((rc = hipMalloc((void **)&(ptr), (size_t)(count) * 4)) != hipSuccess) return rc; if (acct) *acct += (size_t)(count) * 4
+    SA(s.keys_in, keys * rows);
+    if ((rc = hipMemset(s.keys_in, 0, keys * rows * 4)) != hipSuccess) return rc;
+    SA(s.scal, 4); SA(s.pmax, (size_t)nblocks * rows); SA(s.h1g, (size_t)2 * 2048 * rows);
+    if ((rc = hipMemset(s.h1g, 0, (size_t)2048 * 8 * rows)) != hipSuccess) return rc;
     SA(s.uniforms, std::max(n_uniforms, 1)); SA(s.recent, SAMP_THREADS); SA(s.recent_n, 1);
+    SA(s.row, sizeof(SampRow) / 4);
 #undef SA
+    s.rows = rows;
     return hipSuccess;
 }
 
 void samp_free(SampScratch &s) {
-    void *p[] = {s.keys_in, s.scal, s.pmax, s.h1g, s.uniforms, s.recent, s.recent_n};
+    void *p[] = {s.keys_in, s.scal, s.pmax, s.h1g, s.uniforms, s.recent, s.recent_n, s.row};
     for (void *q : p) if (q) (void)hipFree(q);
     s = SampScratch{};
 }
 
-// one sampling decision on `logits` (device); advances ctl / ids / the recent window
-hipError_t launch_sample(const SampScratch &s, float *logits, int vocab, const nl_sample_params &p, int *ctl, int *ids,
-                         hipStream_t st, const EmbedParams *emb = nullptr) {
+SampRow samp_row_of(const nl_sample_params &p) {
+    SampRow r{};
+    r.temp = p.temperature; r.top_p = p.top_p; r.top_k = std::max(p.top_k, 1); r.rep_penalty = p.rep_penalty; r.rep_window = p.rep_window;
+    return r;
+}
+
+// the sampler's launches over `nrows` rows of P.  modes: bit m set -> the select kernel of mode m is launched (a row whose mode's
+// kernel is left out is not sampled).  Three selections, none with a sort (nl_sample.h): temp <= 0 -> argmax of the penalised
+// logits; top_p < 1 -> sampleTopP by weighted radix selection (<= 32768 candidates in the registers of the one workgroup, up to
+// 2^17 streamed out of L2); otherwise sampleTopK by a 2-bit-per-pass selection of the k-th largest logit + a bitonic network over
+// the <= 1024 candidates.  One workgroup per row selects: the rows run side by side.
+hipError_t launch_sample_kernels(const SampleParams &P, int nrows, unsigned modes, hipStream_t st) {
+    const int vocab = P.vocab;
+    hipLaunchKernelGGL(samp_penalty_kernel, dim3(P.nblocks, nrows), dim3(256), 0, st, P);
+    if (modes & (1u << SAMP_TOPP)) {
+        hipLaunchKernelGGL(samp_prob_hist_kernel, dim3((vocab + SAMP_THREADS - 1) / SAMP_THREADS, nrows), dim3(SAMP_THREADS), 0, st, P);
+        if (samp_chunk(vocab) == 32) hipLaunchKernelGGL(samp_select_radix_kernel<32>, dim3(1, nrows), dim3(SAMP_THREADS), 0, st, P);
+        else hipLaunchKernelGGL(samp_select_radix_stream_kernel, dim3(1, nrows), dim3(SAMP_THREADS), 0, st, P);
+    }
+    if (modes & (1u << SAMP_TOPK)) {
+        if (samp_chunk(vocab) == 32) hipLaunchKernelGGL(samp_topk_kernel<false>, dim3(1, nrows), dim3(SAMP_THREADS), 0, st, P);
+        else hipLaunchKernelGGL(samp_topk_kernel<true>, dim3(1, nrows), dim3(SAMP_THREADS), 0, st, P);
+    }
+    if (modes & (1u << SAMP_ARGMAX)) hipLaunchKernelGGL(samp_argmax_select_kernel, dim3(1, nrows), dim3(SAMP_THREADS), 0, st, P);
+    return hipGetLastError();
+}
+
+// scratch slabs and vocabulary of a sampler (the row-dependent pointers are the caller's)
+SampleParams samp_params(const SampScratch &s, int vocab) {
     SampleParams P{};
-    if (emb) { P.embed = 1; P.emb = *emb; }
-    P.logits = logits; P.vocab = vocab; P.temp = p.temperature; P.top_p = p.top_p; P.top_k = std::max(p.top_k, 1);
-    P.rep_penalty = p.rep_penalty; P.recent = s.recent; P.recent_n = s.recent_n; P.rep_window = p.rep_window;
-    P.uniforms = s.uniforms; P.ctl = ctl; P.ids = ids;
-    P.keys_in = s.keys_in;
+    P.vocab = vocab;
+    P.keys_in = s.keys_in; P.keys_stride = (long long)SAMP_THREADS * samp_chunk(vocab);
     P.scal = s.scal; P.pmax = s.pmax; P.nblocks = (vocab + 255) / 256;
     P.h1g = s.h1g; P.nblocks_pen = P.nblocks;
-    // Three selections, none with a sort (nl_sample.h): temp <= 0 -> argmax of the penalised logits; top_p < 1 -> sampleTopP by
-    // weighted radix selection (<= 32768 candidates in the registers of the one workgroup, up to 2^17 streamed out of L2);
-    // otherwise sampleTopK by a 2-bit-per-pass selection of the k-th largest logit + a bitonic network over the <= 1024 candidates
-    P.radix = p.temperature > 0.f && p.top_p < 1.0f ? 1 : 0;
-    hipLaunchKernelGGL(samp_penalty_kernel, dim3(P.nblocks), dim3(256), 0, st, P);
-    if (P.radix) {
-        hipLaunchKernelGGL(samp_prob_hist_kernel, dim3((vocab + SAMP_THREADS - 1) / SAMP_THREADS), dim3(SAMP_THREADS), 0, st, P);
-        if (samp_chunk(vocab) == 32) hipLaunchKernelGGL(samp_select_radix_kernel<32>, dim3(1), dim3(SAMP_THREADS), 0, st, P);
-        else hipLaunchKernelGGL(samp_select_radix_stream_kernel, dim3(1), dim3(SAMP_THREADS), 0, st, P);
-    } else if (p.temperature > 0.f) {
-        if (samp_chunk(vocab) == 32) hipLaunchKernelGGL(samp_topk_kernel<false>, dim3(1), dim3(SAMP_THREADS), 0, st, P);
-        else hipLaunchKernelGGL(samp_topk_kernel<true>, dim3(1), dim3(SAMP_THREADS), 0, st, P);
-    } else {
-        hipLaunchKernelGGL(samp_argmax_select_kernel, dim3(1), dim3(SAMP_THREADS), 0, st, P);
-    }
-    return hipGetLastError();
+    return P;
+}
+
+// one sampling decision on `logits` (device) with the settings the caller uploaded to s.row (p: the same settings, which pick
+// the one select launch); advances ctl / ids / the recent window -- the one-row case of the sampler
+hipError_t launch_sample(const SampScratch &s, float *logits, int vocab, const nl_sample_params &p, int *ctl, int *ids,
+                         hipStream_t st, const EmbedParams *emb = nullptr) {
+    SampleParams P = samp_params(s, vocab);
+    if (emb) { P.embed = 1; P.emb = *emb; }
+    P.logits = logits; P.ld = vocab; P.rows = s.row;
+    P.recent = s.recent; P.recent_n = s.recent_n; P.recent_stride = SAMP_THREADS;
+    P.uniforms = s.uniforms; P.ctl = ctl; P.ids = ids;
+    return launch_sample_kernels(P, 1, 1u << samp_mode(p.temperature, p.top_p), st);
 }
 
 int check_sample_params(nl_engine *e, const nl_sample_params *p) {
@@ -3517,6 +3551,7 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
     }
     const SampScratch &s = e->sp;
     const int n_recent_in = *n_recent;
+    const SampRow row = samp_row_of(*p);
     if (e->fused) {   // a redo after a fused-launch timeout restarts from the logits this call found (take_fused_timeout)
         if (!e->samp_keep) { std::lock_guard<std::mutex> setup(g_setup_mu); HIPCK(e, dalloc(&e->samp_keep, (size_t)e->cfg.vocab, &e->bytes_state)); }
         HIPCK(e, hipMemcpyAsync(e->samp_keep, e->logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
@@ -3527,6 +3562,7 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
         // (its argmax does not advance the state).  ctl.pos is primed to pos - 1 so the first increment lands on pos.
         if ((rc = set_ctl(e, 0, pos - 1, 0, stream))) return rc;
         HIPCK(e, hipMemcpyAsync(s.uniforms, uniforms, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCK(e, hipMemcpyAsync(s.row, &row, sizeof row, hipMemcpyHostToDevice, e->stream));
         if (n_recent_in > 0) HIPCK(e, hipMemcpyAsync(s.recent, recent, (size_t)n_recent_in * 4, hipMemcpyHostToDevice, e->stream));
         *n_recent = n_recent_in;
         HIPCK(e, hipMemcpyAsync(s.recent_n, n_recent, 4, hipMemcpyHostToDevice, e->stream));
@@ -3607,6 +3643,8 @@ int nl_op_sample(int device, float *logits, int vocab, const nl_sample_params *p
         if (hipMemset(d_ctl, 0, CTL_WORDS * 4) != hipSuccess) break;
         if (hipMemcpy(d_logits, logits, (size_t)vocab * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(s.uniforms, &uniform, 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        const SampRow row = samp_row_of(*p);
+        if (hipMemcpy(s.row, &row, sizeof row, hipMemcpyHostToDevice) != hipSuccess) break;
         if (*n_recent > 0 && hipMemcpy(s.recent, recent, (size_t)*n_recent * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(s.recent_n, n_recent, 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (launch_sample(s, d_logits, vocab, *p, d_ctl, d_ids, (hipStream_t)0) != hipSuccess) break;
@@ -3770,6 +3808,147 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
         HIPCK(e, hipStreamSynchronize(e->stream));
         if (attempt == 0 && take_fused_timeout(e)) continue;   // every stream's step again, on the general plan
         break;
+    }
+    return NL_OK;
+}
+
+namespace {
+
+constexpr int BS_MAX_ROWS = QG_TOK;   // rows of one nl_forward_batch_sample call: the LM head's batch
+
+// The block of an nl_forward_batch_sample call of m rows, in 32-bit words: settings [m][8] (SampRow) | uniforms [m] | window
+// lengths [m] | ids [m] | windows [m][1024].  Uploaded whole at the head of the step, read back from the window lengths on.
+struct BsLayout { size_t rows, u, nrec, ids, win, total; };
+BsLayout bs_layout(int m) {
+    const size_t M = (size_t)m;
+    return {0, 8 * M, 9 * M, 10 * M, 11 * M, (11 + (size_t)SAMP_THREADS) * M};
+}
+
+// the sampler over rows [row0, row0 + nrows) of the block `blk` (m rows), row r's logits at logits + (r - row0) * vocab; the
+// scratch slabs are taken from slab 0
+hipError_t launch_block_sample(nl_engine *e, int *blk, int m, int row0, int nrows, float *logits, unsigned modes, hipStream_t st) {
+    const BsLayout L = bs_layout(m);
+    SampleParams P = samp_params(e->bs, e->cfg.vocab);
+    P.logits = logits; P.ld = e->cfg.vocab;
+    P.rows = reinterpret_cast<const SampRow *>(blk + L.rows) + row0;
+    P.uniforms = reinterpret_cast<const float *>(blk + L.u) + row0;
+    P.recent_n = blk + L.nrec + row0;
+    P.ids = blk + L.ids + row0;
+    P.recent = blk + L.win + (size_t)row0 * SAMP_THREADS; P.recent_stride = SAMP_THREADS;
+    return launch_sample_kernels(P, nrows, modes, st);
+}
+
+}  // namespace
+
+int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, const int *pos, int n,
+                            const nl_sample_params *params, const float *uniforms, int *recent, int recent_stride,
+                            int *n_recent, int *next_ids) {
+    if (!e) return NL_ERR_INVALID;
+    if (e->grp) return e->fail(NL_ERR_UNSUPPORTED, "nl_forward_batch_sample: device groups are not supported");
+    if (!streams || !tokens || !pos || n < 0 || (n > 0 && (!params || !uniforms || !recent || !n_recent || !next_ids)))
+        return NL_ERR_INVALID;
+    if (n > e->cfg.max_streams) return e->fail(NL_ERR_INVALID, "batch of %d exceeds max_streams %d", n, e->cfg.max_streams);
+    if (n > BS_MAX_ROWS) return e->fail(NL_ERR_INVALID, "sampled batch of %d exceeds %d rows", n, BS_MAX_ROWS);
+    if (e->cfg.vocab > 131072) return e->fail(NL_ERR_UNSUPPORTED, "on-device sampling covers vocabularies up to 131072, not %d", e->cfg.vocab);
+    int rc;
+    for (int i = 0; i < n; i++) {
+        if ((rc = check_step_args(e, streams[i], tokens[i], pos[i]))) return rc;
+        for (int j = 0; j < i; j++)
+            if (streams[j] == streams[i]) return e->fail(NL_ERR_INVALID, "stream %d appears twice in one batch", streams[i]);
+        if ((rc = check_sample_params(e, &params[i]))) return rc;
+        if (params[i].rep_window > recent_stride)
+            return e->fail(NL_ERR_INVALID, "rep_window %d of row %d exceeds recent_stride %d", params[i].rep_window, i, recent_stride);
+        if (n_recent[i] < 0 || n_recent[i] > params[i].rep_window)
+            return e->fail(NL_ERR_INVALID, "n_recent %d of row %d exceeds rep_window %d", n_recent[i], i, params[i].rep_window);
+    }
+    if (n == 0) return NL_OK;
+    HIPCK(e, hipSetDevice(e->dev));
+    if (int qrc = pd_session_close(e)) return qrc;
+    if (!e->h_bs) {
+        std::lock_guard<std::mutex> setup(g_setup_mu);
+        const size_t words = bs_layout(BS_MAX_ROWS).total;
+        HIPCK(e, samp_alloc(e->bs, e->cfg.vocab, 1, BS_MAX_ROWS, &e->bytes_state));
+        HIPCK(e, dalloc(&e->bs_dev, words, &e->bytes_state));
+        HIPCK(e, hipHostMalloc((void **)&e->h_bs, words * 4, hipHostMallocDefault));
+    }
+    for (int i = 0; i < n; i++)
+        if ((rc = note_positions(e, streams[i], pos[i], 1))) return rc;
+    // every call brings its settings, uniforms and windows again: nothing but KV rows and position marks outlives it
+    const BsLayout L = bs_layout(n);
+    int *const h = e->h_bs;
+    auto pack = [&]() {
+        for (int i = 0; i < n; i++) {
+            reinterpret_cast<SampRow *>(h + L.rows)[i] = samp_row_of(params[i]);
+            reinterpret_cast<float *>(h + L.u)[i] = uniforms[i];
+            h[L.nrec + i] = n_recent[i];
+            memcpy(h + L.win + (size_t)i * SAMP_THREADS, recent + (size_t)i * recent_stride, (size_t)n_recent[i] * 4);
+        }
+    };
+    auto upload = [&](hipStream_t st) { return hipMemcpyAsync(e->bs_dev, h, L.total * 4, hipMemcpyHostToDevice, st); };
+    auto download = [&](hipStream_t st) {
+        return hipMemcpyAsync(h + L.nrec, e->bs_dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, st);
+    };
+    const StepKnobs k;
+    if (n >= process_knobs().batch_min && batch_supported(e)) {
+        // one batched_step with every row's logits (lm_mode 1), the n-row sampler on them, the block in and out around it: one
+        // graph per (rows, position splits, step knobs) -- the settings are data, so any mix of them replays the same graph
+        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc; }
+        nl_engine::Batch &b = e->bt;
+        int nsplit = 1;
+        for (int i = 0; i < n; i++) {
+            b.h_meta[i] = tokens[i];
+            b.h_meta[b.cap + i] = pos[i];
+            b.h_meta[2 * b.cap + i] = streams[i];
+            nsplit = std::max(nsplit, pos[i] / ATT_CH + 1);
+        }
+        pack();
+        auto body = [&](hipStream_t st) -> int {
+            HIPCK(e, upload(st));
+            if (int r2 = batched_step(e, b, st, n, 1, k)) return r2;
+            HIPCK(e, launch_block_sample(e, e->bs_dev, n, 0, n, b.logits, 7u, st));
+            HIPCK(e, download(st));
+            return NL_OK;
+        };
+        hipGraphExec_t exec = nullptr;
+        for (const auto &G : e->bs_graphs)
+            if (G.m == n && G.nsplit == nsplit && G.knobs == k) exec = G.exec;
+        if (!exec && e->use_graph) {
+            std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
+            hipGraph_t gr = nullptr;
+            if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                const int r2 = body(e->stream);
+                const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
+                if (!r2 && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess)
+                    e->bs_graphs.push_back({n, nsplit, k, gr, exec});
+                else { if (gr) (void)hipGraphDestroy(gr); exec = nullptr; }
+            }
+            (void)hipGetLastError();
+        }
+        if (exec) HIPCK(e, hipGraphLaunch(exec, e->stream));
+        else if ((rc = body(e->stream))) return rc;       // (no graphs, or a step whose capture failed: eager)
+        HIPCK(e, hipStreamSynchronize(e->stream));
+    } else {
+        // fewer rows, or a format outside the batch path: every row's single-token step, then the sampler on that row's logits
+        for (int attempt = 0;; attempt++) {
+            pack();
+            HIPCK(e, upload(e->stream));
+            for (int i = 0; i < n; i++) {
+                int *c = e->h_ctl_ring + (size_t)i * CTL_WORDS;
+                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos[i]; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = streams[i];
+                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
+                if ((rc = launch_step(e, pos[i]))) return rc;
+                HIPCK(e, launch_block_sample(e, e->bs_dev, n, i, 1, e->logits, 1u << samp_mode(params[i].temperature, params[i].top_p), e->stream));
+            }
+            HIPCK(e, download(e->stream));
+            HIPCK(e, hipStreamSynchronize(e->stream));
+            if (attempt == 0 && take_fused_timeout(e)) continue;   // every row again, on the general plan, from the caller's windows
+            break;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        next_ids[i] = h[L.ids + i];
+        n_recent[i] = h[L.nrec + i];
+        memcpy(recent + (size_t)i * recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)n_recent[i] * 4);
     }
     return NL_OK;
 }

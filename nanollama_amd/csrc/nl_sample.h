@@ -32,28 +32,66 @@ namespace nl {
 
 constexpr int SAMP_THREADS = 1024;
 
-struct SampleParams {
-    float *logits;
-    int vocab;
+// The sampler works on ROWS: row r (blockIdx.y of every launch) has its own logits, recent window, uniform, scratch slabs and
+// settings.  The settings live in device memory, not in kernel arguments, and every row picks its selection there: the launch
+// sequence of a step depends on the row count and the vocabulary only, so one captured graph serves any mix of settings
+// (nl_forward_batch_sample).  A select kernel whose mode a row does not use returns at once for that row.  One-stream sampling
+// (nl_sample_decode, nl_op_sample) is the one-row case.
+struct SampRow {          // nl_sample_params as the device reads it (8 words)
     float temp, top_p;
-    int top_k;
+    int top_k;            // >= 1
     float rep_penalty;
-    int *recent;          // [rep_window] oldest -> newest
-    int *recent_n;
-    int rep_window;
+    int rep_window;       // <= 1024
+    int pad[3];
+};
+enum { SAMP_ARGMAX = 0, SAMP_TOPP = 1, SAMP_TOPK = 2 };
+// temp <= 0 -> argmax of the penalised logits; top_p < 1 -> sampleTopP; otherwise sampleTopK (go/main.go:191-195, :297-299)
+__host__ __device__ inline int samp_mode(float temp, float top_p) { return !(temp > 0.f) ? SAMP_ARGMAX : top_p < 1.0f ? SAMP_TOPP : SAMP_TOPK; }
+
+struct SampleParams {
+    float *logits;        // row r: logits + r * ld
+    long long ld;
+    int vocab;
+    const SampRow *rows;  // [rows] settings
+    int *recent;          // row r: recent + r * recent_stride, [rep_window] oldest -> newest
+    int *recent_n;        // [rows]
+    int recent_stride;
     const float *uniforms;
-    int *ctl, *ids;
-    float *keys_in;       // [1024 * chunk] unnormalised probabilities of the top-p selection
+    int *ctl, *ids;       // ctl set (one stream): uniform and id of step ctl[CTL_STEP], which the pick advances; else row r's: [r]
+    float *keys_in;       // row r: keys_in + r * keys_stride, [1024 * chunk] unnormalised probabilities of the top-p selection
+    long long keys_stride;
     float *scal;          // (spare scalars)
-    float *pmax;          // [nblocks] workgroup maxima of the penalised logits (samp_penalty_kernel)
+    float *pmax;          // row r: pmax + r * nblocks_pen, workgroup maxima of the penalised logits (samp_penalty_kernel)
     int nblocks;
-    int radix;            // top-p by radix selection (samp_select_radix_kernel): keys_in = p and the level-1 histogram h1g
-    unsigned long long *h1g;   // [2048] sums of candidate weights per level-1 bucket: zeroed by samp_penalty_kernel, filled by
-                               // samp_prob_hist_kernel (all compute units), read by the selecting workgroup
-    int nblocks_pen;      // workgroups of samp_penalty_kernel (pmax entries)
+    unsigned long long *h1g;   // row r: h1g + r * 2048, sums of candidate weights per level-1 bucket: zeroed by samp_penalty_kernel,
+                               // filled by samp_prob_hist_kernel (all compute units), read by the selecting workgroup
+    int nblocks_pen;      // workgroups of samp_penalty_kernel per row (pmax entries)
     int embed;            // the select launch also writes the picked token's embedding row (emb): the next Forward then starts
     EmbedParams emb;      //   at its first layer, as the chained greedy graph does with argmax_embed_kernel
 };
+
+// row blockIdx.y of a launch: its settings and its slices of every per-row array
+struct SampRowView {
+    SampRow s;
+    int mode, slot;       // slot: index into uniforms / ids
+    float *logits, *keys, *pmax;
+    unsigned long long *h1g;
+    int *recent, *recent_n;
+};
+__device__ __forceinline__ SampRowView samp_row(const SampleParams &P) {
+    const int r = blockIdx.y;
+    SampRowView R;
+    R.s = P.rows[r];
+    R.mode = samp_mode(R.s.temp, R.s.top_p);
+    R.slot = P.ctl ? P.ctl[CTL_STEP] : r;
+    R.logits = P.logits + r * P.ld;
+    R.keys = P.keys_in + r * P.keys_stride;
+    R.pmax = P.pmax + (long long)r * P.nblocks_pen;
+    R.h1g = P.h1g + (long long)r * 2048;
+    R.recent = P.recent + (long long)r * P.recent_stride;
+    R.recent_n = P.recent_n + r;
+    return R;
+}
 
 // the embedding lookup that opens the next Forward (embed_kernel), by the workgroup that picked the token
 __device__ __forceinline__ void samp_embed_tail(const SampleParams &P, int token) {
@@ -68,39 +106,44 @@ __device__ __forceinline__ void samp_embed_tail(const SampleParams &P, int token
     }
 }
 
-// device scratch of one sampler (one vocabulary)
+// device scratch of a sampler of `rows` rows (one vocabulary): keys_in, pmax and h1g are per-row slabs; uniforms, recent,
+// recent_n and the settings row serve the one-stream paths (a batch brings its own in the call's block)
 struct SampScratch {
     float *keys_in = nullptr, *scal = nullptr, *pmax = nullptr, *uniforms = nullptr;
     unsigned long long *h1g = nullptr;
     int *recent = nullptr, *recent_n = nullptr;
+    SampRow *row = nullptr;
+    int rows = 0;
 };
 
-// vocab / 256 workgroups: repetition penalty on the workgroup's own 256 logits (every workgroup reads the window and
+// vocab / 256 workgroups per row: repetition penalty on the workgroup's own 256 logits (every workgroup reads the window and
 // counts the occurrences of its own ids: the penalty of a token depends on its own logit and its count only, and x / p,
 // x * p keep the sign, so "once per occurrence in window order" is "count times"), then the workgroup's maximum
 __global__ void __launch_bounds__(256) samp_penalty_kernel(SampleParams P) {
     __shared__ float red[4];
     __shared__ int win[SAMP_THREADS];
+    const SampRowView R = samp_row(P);
     const int tid = threadIdx.x, i = blockIdx.x * 256 + tid;
-    const int n = sload_i32(P.recent_n);
-    float v = P.logits[min(i, P.vocab - 1)];
-    if (P.radix)      // the level-1 histogram of this step's selection (filled by the next launch)
-        for (int j = i; j < 2048; j += (int)gridDim.x * 256) P.h1g[j] = 0;
-    if (P.rep_penalty > 1.0f && n > 0) {
-        for (int s = tid; s < n; s += 256) win[s] = P.recent[s];
+    const int n = sload_i32(R.recent_n);
+    const float pen = R.s.rep_penalty;
+    float v = R.logits[min(i, P.vocab - 1)];
+    if (R.mode == SAMP_TOPP)      // the level-1 histogram of this step's selection (filled by the next launch)
+        for (int j = i; j < 2048; j += (int)gridDim.x * 256) R.h1g[j] = 0;
+    if (pen > 1.0f && n > 0) {
+        for (int s = tid; s < n; s += 256) win[s] = R.recent[s];
         __syncthreads();
         int count = 0;
         for (int s = 0; s < n; s++) count += win[s] == i ? 1 : 0;
         if (count && i < P.vocab) {
-            for (int c = 0; c < count; c++) v = v > 0.f ? v / P.rep_penalty : v * P.rep_penalty;
-            P.logits[i] = v;
+            for (int c = 0; c < count; c++) v = v > 0.f ? v / pen : v * pen;
+            R.logits[i] = v;
         }
     }
     float m = i < P.vocab ? v : -INFINITY;
     m = wave_max_f32(m);
     if ((tid & 63) == 0) red[tid >> 6] = m;
     __syncthreads();
-    if (tid == 0) P.pmax[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (tid == 0) R.pmax[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
 // The top-p path's probabilities p_i = f32(exp(f64((l_i - max) / temp))), plus level 1 of the selection's histograms, built HERE by
@@ -117,18 +160,20 @@ __device__ __forceinline__ unsigned long long samp_weight_of(unsigned k) {   // 
 __global__ void __launch_bounds__(SAMP_THREADS) samp_prob_hist_kernel(SampleParams P) {
     __shared__ float red[SAMP_THREADS / 64];
     __shared__ unsigned long long hl[2048];
+    const SampRowView R = samp_row(P);
+    if (R.mode != SAMP_TOPP) return;
     const int tid = threadIdx.x, i = blockIdx.x * SAMP_THREADS + tid;
-    const float l = P.logits[min(i, P.vocab - 1)];
+    const float l = R.logits[min(i, P.vocab - 1)];
     hl[tid] = 0; hl[tid + 1024] = 0;
-    float gmax = tid < P.nblocks_pen ? P.pmax[tid] : -INFINITY;          // (<= 512 workgroup maxima)
+    float gmax = tid < P.nblocks_pen ? R.pmax[tid] : -INFINITY;          // (<= 512 workgroup maxima)
     gmax = wave_max_f32(gmax);
     if ((tid & 63) == 0) red[tid >> 6] = gmax;
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < SAMP_THREADS / 64; w++) gmax = fmaxf(gmax, red[w]);
     if (i < P.vocab) {
-        const float key = (float)exp((double)((l - gmax) / P.temp));
-        P.keys_in[i] = key;
+        const float key = (float)exp((double)((l - gmax) / R.s.temp));
+        R.keys[i] = key;
         const unsigned kb = __float_as_uint(key);
         if (kb >= SAMP_KEY_MIN) atomicAdd(&hl[(kb - SAMP_KEY_MIN) >> SAMP_S1], samp_weight_of(kb));
     }
@@ -136,7 +181,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_prob_hist_kernel(SamplePara
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         const unsigned long long v = hl[tid + q * 1024];
-        if (v) atomicAdd(&P.h1g[tid + q * 1024], v);
+        if (v) atomicAdd(&R.h1g[tid + q * 1024], v);
     }
 }
 
@@ -170,27 +215,29 @@ __device__ __forceinline__ void samp_each_key(const unsigned *kin, int V, F f) {
 
 // the end of every selecting launch: embedding row of the pick (opens the next Forward), recent window append / drop-oldest
 // (go/main.go:197-200), decode state.  Called by all SAMP_THREADS threads of the one workgroup.
-__device__ __forceinline__ void samp_finish(const SampleParams &P, int pick, int step) {
-    const int tid = threadIdx.x;
+__device__ __forceinline__ void samp_finish(const SampleParams &P, const SampRowView &R, int pick) {
+    const int tid = threadIdx.x, win = R.s.rep_window;
     samp_embed_tail(P, pick);
-    const int n = *P.recent_n;
+    const int n = *R.recent_n;
     int shifted = 0;
-    if (P.rep_window > 0 && n >= P.rep_window && tid + 1 < n) shifted = P.recent[tid + 1];   // rep_window <= 1024
+    if (win > 0 && n >= win && tid + 1 < n) shifted = R.recent[tid + 1];   // rep_window <= 1024
     __syncthreads();
-    if (P.rep_window > 0) {
-        if (n >= P.rep_window) {
-            if (tid + 1 < n) P.recent[tid] = shifted;
-            if (tid == 0) P.recent[n - 1] = pick;
+    if (win > 0) {
+        if (n >= win) {
+            if (tid + 1 < n) R.recent[tid] = shifted;
+            if (tid == 0) R.recent[n - 1] = pick;
         } else if (tid == 0) {
-            P.recent[n] = pick;
-            *P.recent_n = n + 1;
+            R.recent[n] = pick;
+            *R.recent_n = n + 1;
         }
     }
     if (tid == 0) {
-        P.ids[step] = pick;
-        P.ctl[CTL_STEP] = step + 1;
-        P.ctl[CTL_TOKEN] = pick;
-        P.ctl[CTL_POS] = P.ctl[CTL_POS] + 1;
+        P.ids[R.slot] = pick;
+        if (P.ctl) {
+            P.ctl[CTL_STEP] = R.slot + 1;
+            P.ctl[CTL_TOKEN] = pick;
+            P.ctl[CTL_POS] = P.ctl[CTL_POS] + 1;
+        }
     }
 }
 
@@ -199,12 +246,13 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_argmax_select_kernel(Sample
     __shared__ float bval[SAMP_THREADS / 64];
     __shared__ int bidx[SAMP_THREADS / 64];
     __shared__ int s_pick;
+    const SampRowView R = samp_row(P);
+    if (R.mode != SAMP_ARGMAX) return;
     const int tid = threadIdx.x, V = P.vocab;
-    const int step = P.ctl[CTL_STEP];
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int i = tid; i < V; i += SAMP_THREADS) {
-        const float v = P.logits[i];
+        const float v = R.logits[i];
         if (v > best || idx == 0x7fffffff) { best = v; idx = i; }
     }
 #pragma unroll
@@ -221,7 +269,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_argmax_select_kernel(Sample
         s_pick = idx == 0x7fffffff ? 0 : idx;
     }
     __syncthreads();
-    samp_finish(P, s_pick, step);
+    samp_finish(P, R, s_pick);
 }
 
 // ---- sampleTopK (go/main.go:294-343) without a sort of the vocabulary ----------------------------------------------------------
@@ -288,16 +336,17 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_topk_kernel(SampleParams P)
     __shared__ unsigned wtot[SAMP_THREADS / 64];
     __shared__ float prob[SAMP_THREADS];
     __shared__ int s_pick;
+    const SampRowView R = samp_row(P);
+    if (R.mode != SAMP_TOPK) return;
     const int tid = threadIdx.x, V = P.vocab;
-    const int step = P.ctl[CTL_STEP];
-    const float u = P.uniforms[step];
-    const int K = min(min(P.top_k, V), SAMP_THREADS);
-    const unsigned *lg = reinterpret_cast<const unsigned *>(P.logits);
+    const float u = P.uniforms[R.slot];
+    const int K = min(min(R.s.top_k, V), SAMP_THREADS);
+    const unsigned *lg = reinterpret_cast<const unsigned *>(R.logits);
     unsigned key[STREAM ? 1 : C];
     const int lo = tid * C;
     if (!STREAM) {
 #pragma unroll
-        for (int k = 0; k < C; k++) key[k] = lo + k < V ? samp_key_of(P.logits[min(lo + k, V - 1)]) : 0u;     // (past the vocabulary: the lowest key, never needed: K <= V)
+        for (int k = 0; k < C; k++) key[k] = lo + k < V ? samp_key_of(R.logits[min(lo + k, V - 1)]) : 0u;     // (past the vocabulary: the lowest key, never needed: K <= V)
     }
     list[tid] = 0;
     // ---- 2. the k-th largest key, two bits per pass ----
@@ -397,7 +446,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_topk_kernel(SampleParams P)
     }
     // ---- 5. the Go loop (go/main.go:325-342): probabilities relative to the largest, sequential sums on one lane ----
     const float v0 = samp_val_of((unsigned)(list[0] >> 32));
-    if (tid < K) prob[tid] = (float)exp((double)((samp_val_of((unsigned)(list[tid] >> 32)) - v0) / P.temp));
+    if (tid < K) prob[tid] = (float)exp((double)((samp_val_of((unsigned)(list[tid] >> 32)) - v0) / R.s.temp));
     __syncthreads();
     if (tid == 0) {
         float sum = 0.f;
@@ -412,7 +461,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_topk_kernel(SampleParams P)
         s_pick = (int)(0xffffffffu - (unsigned)list[sel]);
     }
     __syncthreads();
-    samp_finish(P, s_pick, step);
+    samp_finish(P, R, s_pick);
 }
 
 // ---- top-p without a sort: weighted radix selection in one workgroup -----------------------------------------------
@@ -529,11 +578,12 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_kernel(SampleP
     __shared__ unsigned wcnt[SAMP_THREADS / 64];
     __shared__ unsigned list_n;
     __shared__ int s_pick;
+    const SampRowView R = samp_row(P);
+    if (R.mode != SAMP_TOPP) return;
     const int tid = threadIdx.x, V = P.vocab, lo = tid * C;
-    const int step = P.ctl[CTL_STEP];
-    const float u = P.uniforms[step];
+    const float u = P.uniforms[R.slot];
     unsigned key[C];                                        // bits of p >= 0: unsigned order = float order
-    const unsigned *kin = reinterpret_cast<const unsigned *>(P.keys_in);
+    const unsigned *kin = reinterpret_cast<const unsigned *>(R.keys);
     SAMP_STAMP(0);
 #pragma unroll
     for (int k = 0; k < C; k += 4) {                        // (keys_in holds 1024 * C entries; the tail past vocab is masked)
@@ -547,7 +597,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_kernel(SampleP
     // level 1 comes from samp_prob_hist_kernel (global memory, built by every compute unit); keys relative to SAMP_KEY_MIN
     constexpr unsigned kmin = SAMP_KEY_MIN;
     constexpr int s1 = SAMP_S1, s2 = SAMP_S2;
-    const samp_u64 *const h1 = P.h1g;
+    const samp_u64 *const h1 = R.h1g;
     auto weight_of = [](unsigned k) { return samp_weight_of(k); };
     SAMP_STAMP(2);
     SAMP_STAMP(3);
@@ -624,7 +674,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_kernel(SampleP
     auto tie_rank = [](samp_u64 rem, samp_u64 w) { return rem <= w ? (samp_u64)1 : (rem + w - 1) / w; };
     unsigned dc, dp;
     samp_u64 rem, xcut, xr;
-    const float top_p = P.top_p;
+    const float top_p = R.s.top_p;
     select([top_p](samp_u64 total) { const samp_u64 x = samp_ceil_mul(top_p, total); return x < 1 ? (samp_u64)1 : x; }, dc, rem, xcut);
     stamp_base = 8;
     const samp_u64 wc = weight_of(dc + kmin);
@@ -664,28 +714,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_kernel(SampleP
     }
     __syncthreads();
     SAMP_STAMP(13);
-    const int pick = s_pick == 0x7fffffff ? 0 : s_pick;
-    samp_embed_tail(P, pick);
-    // recent window: append, drop the oldest when full (go/main.go:197-200)
-    const int n = *P.recent_n;
-    int shifted = 0;
-    if (P.rep_window > 0 && n >= P.rep_window && tid + 1 < n) shifted = P.recent[tid + 1];   // rep_window <= 1024
-    __syncthreads();
-    if (P.rep_window > 0) {
-        if (n >= P.rep_window) {
-            if (tid + 1 < n) P.recent[tid] = shifted;
-            if (tid == 0) P.recent[n - 1] = pick;
-        } else if (tid == 0) {
-            P.recent[n] = pick;
-            *P.recent_n = n + 1;
-        }
-    }
-    if (tid == 0) {
-        P.ids[step] = pick;
-        P.ctl[CTL_STEP] = step + 1;
-        P.ctl[CTL_TOKEN] = pick;
-        P.ctl[CTL_POS] = P.ctl[CTL_POS] + 1;
-    }
+    samp_finish(P, R, s_pick == 0x7fffffff ? 0 : s_pick);   // (embedding row, recent window: go/main.go:197-200, decode state)
     SAMP_STAMP(14);
 }
 
@@ -701,15 +730,16 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_stream_kernel(
     __shared__ unsigned wcnt[SAMP_THREADS / 64];
     __shared__ unsigned list_n;
     __shared__ int s_pick;
+    const SampRowView R = samp_row(P);
+    if (R.mode != SAMP_TOPP) return;
     const int tid = threadIdx.x, V = P.vocab;
-    const int step = P.ctl[CTL_STEP];
-    const float u = P.uniforms[step];
-    const unsigned *kin = reinterpret_cast<const unsigned *>(P.keys_in);
+    const float u = P.uniforms[R.slot];
+    const unsigned *kin = reinterpret_cast<const unsigned *>(R.keys);
     if (tid == 0) s_pick = 0x7fffffff;
     int par = 0;
     constexpr unsigned kmin = SAMP_KEY_MIN;                  // level 1 comes from samp_prob_hist_kernel, keys relative to SAMP_KEY_MIN
     constexpr int s1 = SAMP_S1, s2 = SAMP_S2;
-    const samp_u64 *const h1 = P.h1g;
+    const samp_u64 *const h1 = R.h1g;
     auto weight_of = [](unsigned k) { return samp_weight_of(k); };
     __syncthreads();
     auto select = [&](auto x_of, unsigned &dout, samp_u64 &rem, samp_u64 &x) {
@@ -768,7 +798,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_stream_kernel(
     auto tie_rank = [](samp_u64 rem, samp_u64 w) { return rem <= w ? (samp_u64)1 : (rem + w - 1) / w; };
     unsigned dc, dp;
     samp_u64 rem, xcut, xr;
-    const float top_p = P.top_p;
+    const float top_p = R.s.top_p;
     select([top_p](samp_u64 total) { const samp_u64 x = samp_ceil_mul(top_p, total); return x < 1 ? (samp_u64)1 : x; }, dc, rem, xcut);
     const samp_u64 wc = weight_of(dc + kmin);
     const samp_u64 cum = xcut - rem + tie_rank(rem, wc) * wc;
@@ -801,27 +831,7 @@ __global__ void __launch_bounds__(SAMP_THREADS) samp_select_radix_stream_kernel(
         }
     }
     __syncthreads();
-    const int pick = s_pick == 0x7fffffff ? 0 : s_pick;
-    samp_embed_tail(P, pick);
-    const int n = *P.recent_n;
-    int shifted = 0;
-    if (P.rep_window > 0 && n >= P.rep_window && tid + 1 < n) shifted = P.recent[tid + 1];   // rep_window <= 1024
-    __syncthreads();
-    if (P.rep_window > 0) {
-        if (n >= P.rep_window) {
-            if (tid + 1 < n) P.recent[tid] = shifted;
-            if (tid == 0) P.recent[n - 1] = pick;
-        } else if (tid == 0) {
-            P.recent[n] = pick;
-            *P.recent_n = n + 1;
-        }
-    }
-    if (tid == 0) {
-        P.ids[step] = pick;
-        P.ctl[CTL_STEP] = step + 1;
-        P.ctl[CTL_TOKEN] = pick;
-        P.ctl[CTL_POS] = P.ctl[CTL_POS] + 1;
-    }
+    samp_finish(P, R, s_pick == 0x7fffffff ? 0 : s_pick);
 }
 
 }  // namespace nl

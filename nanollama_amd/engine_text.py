@@ -11,6 +11,36 @@ from .model import LlamaModel
 from .tokenizer import Tokenizer
 
 
+OUTPUT_CAP = 8192   # bytes: the reference loop runs while len(output) < 8192 (go/main.go:173)
+
+
+class TextOutput:
+    """The text of one generation as its ids arrive: the pieces' bytes, the output cap and, when `stream` is given, an
+    incremental UTF-8 decode written there piece by piece.  Shared by TextEngine and the batch scheduler."""
+
+    def __init__(self, tokenizer: Tokenizer, stream=None):
+        self.tokenizer, self.stream = tokenizer, stream
+        self.out = bytearray()
+        self.dec = codecs.getincrementaldecoder("utf-8")(errors="replace")
+
+    def add(self, t: int) -> bool:
+        """Append the piece of id t; True when the output reached the cap: the piece that crosses it is the last one
+        emitted, and the caller samples no further token."""
+        piece = self.tokenizer.decode_token_bytes(t)
+        self.out.extend(piece)
+        if self.stream is not None:
+            self.stream.write(self.dec.decode(piece))
+            self.stream.flush()
+        return len(self.out) >= OUTPUT_CAP
+
+    def finish_stream(self) -> None:
+        """What the incremental decoder still holds, and the line end."""
+        self.stream.write(self.dec.decode(b"", final=True) + "\n")
+
+    def text(self) -> str:
+        return bytes(self.out).decode("utf-8", errors="replace")
+
+
 class TextEngine:
     def __init__(self, model: LlamaModel, tokenizer: Tokenizer, rep_penalty: float = 1.15, rep_window: int = 64,
                  seed: Optional[int] = None):
@@ -20,26 +50,15 @@ class TextEngine:
     def generate(self, prompt: str, p: GenParams, stream=None) -> str:
         """Generate (go/main.go:152): streams pieces to `stream` (stdout in the CLI), prints "[N tokens, X tok/s]"."""
         tokens = self.tokenizer.encode(prompt, True)
-        dec = codecs.getincrementaldecoder("utf-8")(errors="replace")
-        out = bytearray()
-
-        def on_token(t: int) -> bool:
-            # the reference loop runs while len(output) < 8192 (go/main.go:173): the piece that crosses the cap is
-            # the last one emitted, and returning True stops the id-level loop right there (no further sample)
-            piece = self.tokenizer.decode_token_bytes(t)
-            out.extend(piece)
-            if stream is not None:
-                stream.write(dec.decode(piece))
-                stream.flush()
-            return len(out) >= 8192
-
-        self.ids.generate_ids(tokens, p, on_token=on_token)
+        out = TextOutput(self.tokenizer, stream)
+        # on_token returning True (the cap) stops the id-level loop right there (no further sample)
+        self.ids.generate_ids(tokens, p, on_token=out.add)
         if stream is not None:
-            stream.write(dec.decode(b"", final=True) + "\n")
+            out.finish_stream()
             if self.ids.last_tokens and self.ids.last_tok_per_s > 0:
                 stream.write("[%d tokens, %.1f tok/s]\n" % (self.ids.last_tokens, self.ids.last_tok_per_s))
             stream.flush()
-        return bytes(out).decode("utf-8", errors="replace")
+        return out.text()
 
     def generate_quiet(self, prompt: str, p: GenParams) -> str:
         """GenerateQuiet (go/main.go:233-291)."""

@@ -114,6 +114,34 @@ class LlamaModel:
             lg.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, ids))
         return [int(ids[i]) for i in range(n)], lg
 
+    def forward_batch_sample(self, streams: List[int], tokens: List[int], pos: List[int], params, uniforms, recents):
+        """One decode step of n streams, each followed by the sampling half of Generate's loop with its own settings, on
+        the device (nl_forward_batch_sample).  params: per row a dict / object with temperature, top_p, top_k,
+        rep_penalty, rep_window; uniforms: one float32 per row; recents: per row its recent window (oldest first).
+        Returns (ids, recents after the step)."""
+        n = len(streams)
+        ia = lambda v: (C.c_int * max(n, 1))(*[int(x) for x in v])
+        get = lambda p, k: p[k] if isinstance(p, dict) else getattr(p, k)
+        ps = (_lib.NlSampleParams * max(n, 1))(*[
+            _lib.NlSampleParams(float(get(p, "temperature")), float(get(p, "top_p")), int(get(p, "top_k")),
+                                float(get(p, "rep_penalty")), int(get(p, "rep_window"))) for p in params])
+        u = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float32).reshape(-1))
+        if len(params) != n or len(tokens) != n or len(pos) != n or len(recents) != n or u.size != n:
+            raise ValueError("one token, position, settings, uniform and window per stream")
+        stride = max([int(get(p, "rep_window")) for p in params] + [1])
+        rec = np.zeros((max(n, 1), stride), dtype=np.int32)
+        nrec = (C.c_int * max(n, 1))()
+        for i, r in enumerate(recents):
+            if len(r) > stride:
+                raise ValueError(f"window of row {i} holds {len(r)} ids, more than rep_window")
+            rec[i, :len(r)] = r
+            nrec[i] = len(r)
+        ids = (C.c_int * max(n, 1))()
+        _lib.check(self._h, _lib.lib().nl_forward_batch_sample(
+            self._h, ia(streams), ia(tokens), ia(pos), n, ps, u.ctypes.data_as(C.POINTER(C.c_float)),
+            rec.ctypes.data_as(C.POINTER(C.c_int)), stride, nrec, ids))
+        return [int(ids[i]) for i in range(n)], [[int(t) for t in rec[i, :nrec[i]]] for i in range(n)]
+
     def set_gamma(self, indices, values) -> None:
         """model.Gamma = gamma (go/main.go:79): indices int32 [n], values [n, dim] float32 or float16."""
         idx = np.ascontiguousarray(indices, dtype=np.int32)

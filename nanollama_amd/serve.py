@@ -5,14 +5,17 @@
     GET  /health  {"status","params_millions","layers","dim","heads","kv_heads","vocab_size","gamma_loaded"}
 
 One generation at a time (the model handle is single-caller): a lock around GenerateQuiet, as go/serve.go:56,106-108.
+With --parallel N the engine is a BatchScheduler (batch_serve.py): concurrent requests decode as one batch, no lock.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import threading
 from dataclasses import replace
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 
+from .batch_serve import BatchScheduler, RequestError
 from .engine import GenParams
 
 UI_HTML = b"""<!doctype html><html><head><meta charset="utf-8"><title>nanollama</title>
@@ -50,8 +53,11 @@ def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
         params = replace(params, temperature=float(req["temperature"]))
     if isinstance(req.get("top_k"), (int, float)) and req["top_k"] > 0:
         params = replace(params, top_k=int(req["top_k"]))
-    with lock:
-        result = engine.generate_quiet(prompt, params)
+    try:
+        with lock:
+            result = engine.generate_quiet(prompt, params)
+    except RequestError as exc:             # (batch scheduler: settings it cannot serve, or an engine error)
+        return exc.status, str(exc)
     return 200, {"response": result}
 
 
@@ -65,7 +71,8 @@ def handle_health(engine):
 
 
 def make_handler(engine, defaults: GenParams):
-    lock = threading.Lock()
+    # a BatchScheduler takes concurrent requests itself (its worker owns the handle); a TextEngine is single-caller
+    lock = contextlib.nullcontext() if isinstance(engine, BatchScheduler) else threading.Lock()
 
     class Handler(BaseHTTPRequestHandler):
         def log_message(self, fmt, *args):  # quiet
@@ -115,9 +122,14 @@ def make_handler(engine, defaults: GenParams):
     return Handler
 
 
+class _BatchHTTPServer(ThreadingHTTPServer):
+    request_queue_size = 128     # a batching server's clients connect at once (the default backlog of 5 resets some)
+
+
 def run_server(engine, defaults: GenParams, port: int) -> None:
     """runServer go/serve.go:54-131"""
-    srv = ThreadingHTTPServer(("", port), make_handler(engine, defaults))
+    srv_cls = _BatchHTTPServer if isinstance(engine, BatchScheduler) else ThreadingHTTPServer
+    srv = srv_cls(("", port), make_handler(engine, defaults))
     print(f"[nanollama] web UI at http://localhost:{port}")
     try:
         srv.serve_forever()

@@ -236,6 +236,13 @@ NL_API int nl_op_gran16_soak(int device, int n, unsigned iters, unsigned long lo
  * place, as in the reference) is [vocab]; recent (in/out, capacity rep_window) / n_recent follow :197-200. */
 NL_API int nl_op_sample(int device, float *logits, int vocab, const nl_sample_params *p, float uniform,
                         int *recent, int *n_recent, int *picked);
+/* The n-row sampler of nl_forward_batch_sample on host logits: row i (logits + i * vocab, in/out: penalised in place) is
+ * sampled with params[i] and uniforms[i]; its window is recent + i * recent_stride (n_recent[i] ids, oldest first, in/out)
+ * and its pick lands in picked[i].  1 <= n <= 64; the argument checks of nl_forward_batch_sample (vocabularies above 131072
+ * return NL_ERR_UNSUPPORTED).  The launches are the batch call's, on a fresh 64-row scratch whose per-row slabs are
+ * poisoned first, so a row reading a scratch word it did not write in this call does not go unseen. */
+NL_API int nl_op_sample_rows(int device, float *logits, int vocab, int n, const nl_sample_params *params,
+                             const float *uniforms, int *recent, int recent_stride, int *n_recent, int *picked);
 
 /* == tensor-parallel communicator (RCCL over xGMI) ========================= */
 #define NL_COMM_ID_BYTES 128

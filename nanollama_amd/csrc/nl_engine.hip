@@ -3825,11 +3825,13 @@ BsLayout bs_layout(int m) {
 }
 
 // the sampler over rows [row0, row0 + nrows) of the block `blk` (m rows), row r's logits at logits + (r - row0) * vocab; the
-// scratch slabs are taken from slab 0
-hipError_t launch_block_sample(nl_engine *e, int *blk, int m, int row0, int nrows, float *logits, unsigned modes, hipStream_t st) {
+// scratch slabs of s (a sampler of BS_MAX_ROWS rows) are taken from slab 0.  Shared by nl_forward_batch_sample and
+// nl_op_sample_rows, so the op runs the batch path's launches.
+hipError_t launch_block_sample(const SampScratch &s, int vocab, int *blk, int m, int row0, int nrows, float *logits, unsigned modes,
+                               hipStream_t st) {
     const BsLayout L = bs_layout(m);
-    SampleParams P = samp_params(e->bs, e->cfg.vocab);
-    P.logits = logits; P.ld = e->cfg.vocab;
+    SampleParams P = samp_params(s, vocab);
+    P.logits = logits; P.ld = vocab;
     P.rows = reinterpret_cast<const SampRow *>(blk + L.rows) + row0;
     P.uniforms = reinterpret_cast<const float *>(blk + L.u) + row0;
     P.recent_n = blk + L.nrec + row0;
@@ -3905,7 +3907,7 @@ int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, 
         auto body = [&](hipStream_t st) -> int {
             HIPCK(e, upload(st));
             if (int r2 = batched_step(e, b, st, n, 1, k)) return r2;
-            HIPCK(e, launch_block_sample(e, e->bs_dev, n, 0, n, b.logits, 7u, st));
+            HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n, 0, n, b.logits, 7u, st));
             HIPCK(e, download(st));
             return NL_OK;
         };
@@ -3937,7 +3939,7 @@ int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, 
                 c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos[i]; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = streams[i];
                 HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
                 if ((rc = launch_step(e, pos[i]))) return rc;
-                HIPCK(e, launch_block_sample(e, e->bs_dev, n, i, 1, e->logits, 1u << samp_mode(params[i].temperature, params[i].top_p), e->stream));
+                HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n, i, 1, e->logits, 1u << samp_mode(params[i].temperature, params[i].top_p), e->stream));
             }
             HIPCK(e, download(e->stream));
             HIPCK(e, hipStreamSynchronize(e->stream));
@@ -3951,6 +3953,61 @@ int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, 
         memcpy(recent + (size_t)i * recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)n_recent[i] * 4);
     }
     return NL_OK;
+}
+
+int nl_op_sample_rows(int device, float *logits, int vocab, int n, const nl_sample_params *params, const float *uniforms,
+                      int *recent, int recent_stride, int *n_recent, int *picked) {
+    if (!logits || vocab <= 0 || n < 1 || n > BS_MAX_ROWS || !params || !uniforms || !recent || !n_recent || !picked)
+        return NL_ERR_INVALID;
+    if (vocab > 131072) return NL_ERR_UNSUPPORTED;
+    for (int i = 0; i < n; i++) {
+        if (int rc = check_sample_params(nullptr, &params[i])) return rc;
+        if (params[i].rep_window > recent_stride || n_recent[i] < 0 || n_recent[i] > params[i].rep_window) return NL_ERR_INVALID;
+    }
+    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
+    // the block of nl_forward_batch_sample, packed the same way
+    const BsLayout L = bs_layout(n);
+    std::vector<int> h(L.total, 0);
+    for (int i = 0; i < n; i++) {
+        reinterpret_cast<SampRow *>(h.data() + L.rows)[i] = samp_row_of(params[i]);
+        reinterpret_cast<float *>(h.data() + L.u)[i] = uniforms[i];
+        h[L.nrec + i] = n_recent[i];
+        memcpy(h.data() + L.win + (size_t)i * SAMP_THREADS, recent + (size_t)i * recent_stride, (size_t)n_recent[i] * 4);
+    }
+    const size_t lg_bytes = (size_t)n * vocab * 4;
+    SampScratch s;
+    float *d_logits = nullptr;
+    int *d_blk = nullptr;
+    int rc = NL_ERR_HIP;
+    do {
+        if (samp_alloc(s, vocab, 1, BS_MAX_ROWS) != hipSuccess) break;
+        if (hipMalloc((void **)&d_logits, lg_bytes) != hipSuccess || hipMalloc((void **)&d_blk, L.total * 4) != hipSuccess) break;
+        // poison every word a row's launches write before they read it (pmax, h1g, keys_in below the vocabulary): a kernel that
+        // read a word it did not write in this call would see 0xFF bytes here, where the handle's long-lived scratch holds the
+        // previous step's values.  The keys_in tail past the vocabulary keeps samp_alloc's zeroes: the select kernels load it
+        // and mask it.
+        const int nblocks = (vocab + 255) / 256;
+        const size_t kstride = (size_t)SAMP_THREADS * samp_chunk(vocab);
+        if (hipMemset(s.pmax, 0xFF, (size_t)nblocks * BS_MAX_ROWS * 4) != hipSuccess) break;
+        if (hipMemset(s.h1g, 0xFF, (size_t)2048 * 8 * BS_MAX_ROWS) != hipSuccess) break;
+        if (hipMemset2D(s.keys_in, kstride * 4, 0xFF, (size_t)vocab * 4, BS_MAX_ROWS) != hipSuccess) break;
+        if (hipMemcpy(d_logits, logits, lg_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_blk, h.data(), L.total * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (launch_block_sample(s, vocab, d_blk, n, 0, n, d_logits, 7u, (hipStream_t)0) != hipSuccess) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(h.data() + L.nrec, d_blk + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (hipMemcpy(logits, d_logits, lg_bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
+        for (int i = 0; i < n; i++) {
+            picked[i] = h[L.ids + i];
+            n_recent[i] = h[L.nrec + i];
+            memcpy(recent + (size_t)i * recent_stride, h.data() + L.win + (size_t)i * SAMP_THREADS, (size_t)n_recent[i] * 4);
+        }
+        rc = NL_OK;
+    } while (0);
+    samp_free(s);
+    if (d_logits) (void)hipFree(d_logits);
+    if (d_blk) (void)hipFree(d_blk);
+    return rc;
 }
 
 int nl_synchronize(nl_handle e) {

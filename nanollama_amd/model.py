@@ -379,6 +379,38 @@ def op_sample(logits: np.ndarray, temperature: float, top_p: float, top_k: int, 
     return picked.value, lg, [int(rec[i]) for i in range(nrec.value)]
 
 
+def op_sample_rows(logits: np.ndarray, params, uniforms, recents, device: int = 0):
+    """The n-row sampler of a sampled decode batch (nl_op_sample_rows) on host logits [n, vocab]: params per row a dict /
+    object with temperature, top_p, top_k, rep_penalty, rep_window; one float32 uniform and one window per row.
+    Returns (picked ids, logits after the in-place penalty, windows afterwards)."""
+    lg = np.array(logits, dtype=np.float32, copy=True, order="C")
+    if lg.ndim != 2:
+        raise ValueError("logits must be [rows, vocab]")
+    n, vocab = lg.shape
+    get = lambda p, k: p[k] if isinstance(p, dict) else getattr(p, k)
+    ps = (_lib.NlSampleParams * max(n, 1))(*[
+        _lib.NlSampleParams(float(get(p, "temperature")), float(get(p, "top_p")), int(get(p, "top_k")),
+                            float(get(p, "rep_penalty")), int(get(p, "rep_window"))) for p in params])
+    u = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float32).reshape(-1))
+    if len(params) != n or len(recents) != n or u.size != n:
+        raise ValueError("one settings row, uniform and window per logits row")
+    stride = max([int(get(p, "rep_window")) for p in params] + [1])
+    rec = np.zeros((max(n, 1), stride), dtype=np.int32)
+    nrec = (C.c_int * max(n, 1))()
+    for i, r in enumerate(recents):
+        if len(r) > stride:
+            raise ValueError(f"window of row {i} holds {len(r)} ids, more than rep_window")
+        rec[i, :len(r)] = r
+        nrec[i] = len(r)
+    picked = (C.c_int * max(n, 1))()
+    rc = _lib.lib().nl_op_sample_rows(device, lg.ctypes.data_as(C.POINTER(C.c_float)), int(vocab), int(n), ps,
+                                      u.ctypes.data_as(C.POINTER(C.c_float)), rec.ctypes.data_as(C.POINTER(C.c_int)),
+                                      stride, nrec, picked)
+    if rc != 0:
+        raise _lib.NlError(rc, "nl_op_sample_rows")
+    return [int(picked[i]) for i in range(n)], lg, [[int(t) for t in rec[i, :nrec[i]]] for i in range(n)]
+
+
 def op_exp(x: np.ndarray, device: int = 0) -> np.ndarray:
     """float32(exp(float64(x))) as the forward kernels compute it (go/quant.go:619, :629-631)."""
     x = np.ascontiguousarray(x, dtype=np.float32)

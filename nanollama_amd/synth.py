@@ -183,13 +183,30 @@ def _draw_qrand(shape: ModelShape, seed: int, ckpt_name: str, tshape, kind: str,
     return raw
 
 
+def _override(arr: np.ndarray, tshape, gname: str) -> np.ndarray:
+    a = np.ascontiguousarray(arr, dtype=np.float32)
+    if a.shape != tuple(tshape):
+        raise ValueError(f"override of {gname}: shape {a.shape}, the tensor is {tuple(tshape)}")
+    return a
+
+
 def generate_gguf(path: str, shape: ModelShape, wtype: str = "q8_0", seed: Optional[int] = None,
-                  mode: str = "float", keep_float: bool = False, stream_scale: float = 1.0) -> Dict[str, np.ndarray]:
+                  mode: str = "float", keep_float: bool = False, stream_scale: float = 1.0,
+                  overrides: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
     """Write a random-weight GGUF.  Returns {gguf_name: float32 weights} when
     keep_float (test-sized models only).  stream_scale (float mode): the embedding and the two projections that write the
     residual stream (attention output, down) are multiplied by it -- a model whose residual stream lives at that magnitude
-    while everything behind an RMSNorm stays O(1)."""
+    while everything behind an RMSNorm stays O(1).  overrides: {gguf_name: float32 array of the tensor's shape} replaces
+    the drawn values of those tensors before they are encoded (crafted weights, e.g. an LM head with tied rows); the
+    other tensors are drawn as without it."""
     t = WTYPES[wtype]
+    overrides = overrides or {}
+    names = {g for _, g, _, _ in tensor_plan(shape)}
+    for gname, arr in overrides.items():
+        if gname not in names:
+            raise ValueError(f"override of {gname}: no such tensor")
+    if overrides and (mode == "qrand" or t in QRAND_ONLY):
+        raise ValueError("overrides need mode='float' and a format with a quantiser")
     if seed is None:
         seed = TIER_SEED.get(shape.name, 4242)
     w = GGUFWriter(path)
@@ -222,6 +239,8 @@ def generate_gguf(path: str, shape: ModelShape, wtype: str = "q8_0", seed: Optio
     for ckpt, gname, tshape, kind in tensor_plan(shape):
         if kind in ("norm", "bias"):
             f32 = draw_float(shape, seed, ckpt, tshape, kind)
+            if gname in overrides:
+                f32 = _override(overrides[gname], tshape, gname)
             w.add_tensor_raw(gname, quant.to_f32_bytes(f32), GGML_F32, tshape)
             if keep_float:
                 floats[gname] = f32
@@ -232,6 +251,8 @@ def generate_gguf(path: str, shape: ModelShape, wtype: str = "q8_0", seed: Optio
         f32 = draw_float(shape, seed, ckpt, tshape, kind)
         if stream_scale != 1.0 and (kind == "embedding" or ckpt.endswith(("attn.c_proj.weight", "ffn.down_proj.weight"))):
             f32 = (f32 * np.float32(stream_scale)).astype(np.float32)
+        if gname in overrides:
+            f32 = _override(overrides[gname], tshape, gname)
         w.add_tensor_raw(gname, quant.encode(f32, t), t, tshape)
         if keep_float:
             floats[gname] = f32

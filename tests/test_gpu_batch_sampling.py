@@ -72,20 +72,36 @@ def _model_path(tmp_path, kind):
     return p
 
 
-def _drive(hip, g, n, steps, start, seed, shadow_flags=0, dev_flags=0, switch_at=None):
-    """n streams from prompt positions `start` for `steps` fed-back steps on a handle and its shadow; returns the ids."""
+# every row's mode rotates on every step (_drive(rotate=True)): argmax -> top-p -> top-k
+ROTATE = [dict(temperature=0.0, top_p=0.9, top_k=50, rep_penalty=1.3),
+          dict(temperature=0.9, top_p=0.9, top_k=50, rep_penalty=1.15),
+          dict(temperature=1.1, top_p=1.0, top_k=50, rep_penalty=1.15)]
+
+
+def _drive(hip, g, n, steps, start, seed, shadow_flags=0, dev_flags=0, switch_at=None, phases=None, rotate=False,
+           go_rule=False, check_logits=None, tied=()):
+    """n streams from prompt positions `start` for `steps` fed-back steps on a handle and its shadow; returns the ids.
+    phases: row counts of successive runs of `steps` steps on the same two handles (rows = streams [0, m); a stream keeps its
+    position, token and window from phase to phase; start then covers max(phases) streams); rotate: every row's settings
+    rotate through ROTATE on every step; go_rule: top-p picks are also compared with the literal Go chain -- every difference
+    at a boundary (margin < 5e-4), at most max(2, trials // 8) of them up to vocabulary 50000; check_logits(row logits): a
+    precondition asserted on the shadow's logits of every row and step.  tied: ids whose logits are one value on every row
+    (a crafted LM head): a difference where the device's or the Go chain's pick is one of them is a walk over thousands of
+    equal terms, where the Go chain's float32 sum drifts by many of them -- the reason the cap stops at 50000 -- so it is held
+    to the margin rule and counted apart, and the cap applies to the other differences."""
+    phases = phases or [n]
+    N = max(phases)
     vocab = g.meta.vocab_size
-    dev = hip.load_llama_model(g, max_streams=max(n, 1), flags=dev_flags)
-    sh = hip.load_llama_model(g, max_streams=max(n, 1), flags=shadow_flags)
+    dev = hip.load_llama_model(g, max_streams=max(N, 1), flags=dev_flags)
+    sh = hip.load_llama_model(g, max_streams=max(N, 1), flags=shadow_flags)
     rng = np.random.Generator(np.random.PCG64(seed))
     try:
-        streams = list(range(n))
-        prompts = [[int(t) for t in rng.integers(3, vocab, size=start[i] + 1)] for i in range(n)]
-        for i in range(n):
+        prompts = [[int(t) for t in rng.integers(3, vocab, size=start[i] + 1)] for i in range(N)]
+        for i in range(N):
             if start[i] > 0:
                 dev.prefill(prompts[i][:start[i]], pos0=0, stream=i, want_logits=False)
                 sh.prefill(prompts[i][:start[i]], pos0=0, stream=i, want_logits=False)
-        params = [dict(SETTINGS[i % len(SETTINGS)]) for i in range(n)]
+        params = [dict(SETTINGS[i % len(SETTINGS)]) for i in range(N)]
         # windows: empty, partial, full with repeated ids
         recents = []
         for i, p in enumerate(params):
@@ -93,29 +109,56 @@ def _drive(hip, g, n, steps, start, seed, shadow_flags=0, dev_flags=0, switch_at
             k = [0, w // 2, w][i % 3] if w else 0
             base = [int(t) for t in rng.integers(0, vocab, size=max(k, 1))]
             recents.append([base[j % 2] for j in range(k)] if i % 3 == 2 else base[:k])
-        tokens = [prompts[i][start[i]] for i in range(n)]
+        tokens = [prompts[i][start[i]] for i in range(N)]
         pos = list(start)
         all_ids = []
-        for step in range(steps):
-            if switch_at is not None and step == switch_at:       # other settings at the same n (no re-capture needed)
-                params = [dict(SETTINGS[(i + 1) % len(SETTINGS)], rep_window=params[i]["rep_window"]) for i in range(n)]
-                params = [dict(p, top_p=1.0 if p["top_p"] < 1.0 else 0.7) for p in params]
-            us = rng.random(n, dtype=np.float32)
-            ids, new_rec = dev.forward_batch_sample(streams, tokens, pos, params, us, recents)
-            _, lg = sh.forward_batch(streams, tokens, pos, want_logits=True)
-            want_ids, want_rec = [], []
-            for i in range(n):
-                t = host_pick(lg[i], params[i], recents[i], us[i], vocab)
-                want_ids.append(t)
-                want_rec.append(sm.push_recent(recents[i], t, params[i]["rep_window"]) if params[i]["rep_window"] > 0 else [])
-            assert ids == want_ids, (step, ids, want_ids)
-            assert new_rec == want_rec, step
-            all_ids.append(ids)
-            recents, tokens, pos = new_rec, ids, [q + 1 for q in pos]
+        go_trials = go_mism = go_tied = 0
+        tied_set = set(tied)
+        gstep = 0
+        for m in phases:
+            streams = list(range(m))
+            for step in range(steps):
+                if switch_at is not None and step == switch_at:   # other settings at the same n (no re-capture needed)
+                    params = [dict(SETTINGS[(i + 1) % len(SETTINGS)], rep_window=params[i]["rep_window"]) for i in range(N)]
+                    params = [dict(p, top_p=1.0 if p["top_p"] < 1.0 else 0.7) for p in params]
+                cur = params[:m]
+                if rotate:
+                    cur = [dict(ROTATE[(i + gstep) % len(ROTATE)], rep_window=params[i]["rep_window"]) for i in range(m)]
+                us = rng.random(m, dtype=np.float32)
+                ids, new_rec = dev.forward_batch_sample(streams, tokens[:m], pos[:m], cur, us, recents[:m])
+                _, lg = sh.forward_batch(streams, tokens[:m], pos[:m], want_logits=True)
+                want_ids, want_rec = [], []
+                for i in range(m):
+                    if check_logits is not None:
+                        check_logits(lg[i])
+                    t = host_pick(lg[i], cur[i], recents[i], us[i], vocab)
+                    want_ids.append(t)
+                    want_rec.append(sm.push_recent(recents[i], t, cur[i]["rep_window"]) if cur[i]["rep_window"] > 0 else [])
+                    if go_rule and cur[i]["temperature"] > 0 and cur[i]["top_p"] < 1.0:
+                        plg = sm.apply_penalty(lg[i], recents[i], cur[i]["rep_penalty"], vocab)
+                        go_trials += 1
+                        go = sm.go_top_p(plg, cur[i]["temperature"], cur[i]["top_p"], us[i])
+                        if t != go:
+                            assert sm.device_top_p(plg, cur[i]["temperature"], cur[i]["top_p"], us[i])[1] < 5e-4, (m, step, i)
+                            if t in tied_set or go in tied_set:
+                                go_tied += 1
+                            else:
+                                go_mism += 1
+                assert ids == want_ids, (m, step, ids, want_ids)
+                assert new_rec == want_rec, (m, step)
+                all_ids.append(ids)
+                recents[:m], tokens[:m], pos[:m] = new_rec, ids, [q + 1 for q in pos[:m]]
+                gstep += 1
         # the KV state is the same: the next step's logits are bitwise the shadow's
-        _, a = dev.forward_batch(streams, tokens, pos, want_logits=True)
-        _, b = sh.forward_batch(streams, tokens, pos, want_logits=True)
+        streams = list(range(phases[-1]))
+        _, a = dev.forward_batch(streams, tokens[:phases[-1]], pos[:phases[-1]], want_logits=True)
+        _, b = sh.forward_batch(streams, tokens[:phases[-1]], pos[:phases[-1]], want_logits=True)
         assert a.tobytes() == b.tobytes()
+        if go_rule:
+            print(f"V={vocab}: {go_mism + go_tied} of {go_trials} top-p picks differ from the Go chain, {go_tied} of them "
+                  f"on a tied id")
+            if vocab <= 50000:
+                assert go_mism <= max(2, go_trials // 8), (vocab, go_mism, go_trials)
         return all_ids
     finally:
         dev.close()
@@ -155,6 +198,52 @@ def test_no_graph_handle_gives_the_same_ids(hip, tmp_path):
         a = _drive(hip, g, 16, 8, start, 11)
         b = _drive(hip, g, 16, 8, start, 11, dev_flags=_lib.NL_FLAG_NO_GRAPH, shadow_flags=_lib.NL_FLAG_NO_GRAPH)
         assert a == b
+
+
+ZERO_ROWS = 64
+
+
+def _crafted_path(tmp_path, wt, vocab, dim):
+    """A model whose LM head (output.weight) is crafted: ids [0, V/3) copy one row (exact ties on every stream), the ZERO_ROWS
+    ids after them are zero rows (logits of exactly 0), id V - 2 is a row scaled x64 (dominant or far below, by the stream's
+    sign), the rest are the drawn random rows."""
+    shape = synth.ModelShape(f"bs_cr{vocab}", 1, dim, 4, 2, vocab, seq_len=128, interm=2 * dim)
+    head = synth.draw_float(shape, 307, "output.weight", (vocab, dim), "matrix")
+    third = vocab // 3
+    head[:third] = head[vocab - 1]
+    head[third:third + ZERO_ROWS] = 0.0
+    head[vocab - 2] *= np.float32(64.0)
+    p = str(tmp_path / f"crafted_{wt}_{vocab}.gguf")
+    synth.generate_gguf(p, shape, wt, 307, overrides={"output.weight": head})
+    return p
+
+
+def _crafted_preconditions(vocab):
+    third = vocab // 3
+
+    def check(lg):
+        # the edges are reached: >= V/3 - 1 bitwise-equal logits, the zero block exactly 0
+        _, counts = np.unique(lg.view(np.uint32), return_counts=True)
+        assert counts.max() >= third - 1, ("ties lost in the LM head", counts.max(), third)
+        assert np.all(lg[third:third + ZERO_ROWS] == 0.0), "the zero rows do not give logits of 0"
+    return check
+
+
+@pytest.mark.parametrize("wt,vocab,dim", [("q8_0", 32768, 128), ("q8_0", 32769, 128), ("q8_0", 131072, 128),
+                                          ("q4_0", 32768, 256)])
+def test_crafted_logits_rotating_modes_and_row_counts(hip, tmp_path, wt, vocab, dim):
+    # the batch path on logits with exact ties over a third of the vocabulary, a block of zeros and one token far above or
+    # below the rest (q4_0 with whole 256-column groups: the dghead_kernel LM head); every row's mode rotates on every step and
+    # the row counts on one handle go 64 -> 2 (below NL_BATCH_MIN: the per-row fallback) -> 17 (another captured graph) -> 64
+    # (the handle's persistent sampler scratch again), with graphs and without
+    from nanollama_amd import _lib
+    g = gguf.load_gguf(_crafted_path(tmp_path, wt, vocab, dim))
+    start = _starts(64, 0, 60, vocab)
+    kw = dict(phases=[64, 2, 17, 64], rotate=True, go_rule=True, check_logits=_crafted_preconditions(vocab),
+              tied=list(range(vocab // 3)) + [vocab - 1])
+    a = _drive(hip, g, 64, 4, start, 31, **kw)
+    b = _drive(hip, g, 64, 4, start, 31, dev_flags=_lib.NL_FLAG_NO_GRAPH, **kw)
+    assert a == b
 
 
 def test_argument_errors(hip):

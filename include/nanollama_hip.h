@@ -175,6 +175,27 @@ NL_API int nl_forward_batch(nl_handle h, const int *streams, const int *tokens, 
 NL_API int nl_forward_batch_sample(nl_handle h, const int *streams, const int *tokens, const int *pos, int n,
                                    const nl_sample_params *params, const float *uniforms,
                                    int *recent, int recent_stride, int *n_recent, int *next_ids);
+/* One step over n (stream, token, pos) rows in which a stream may appear several times -- the decode rows of running
+ * requests and chunks of the prompts being admitted (go/main.go:160-166 feeds a prompt token by token through Forward;
+ * go/main.go:173-219 decodes).  Result contract: per stream, as if its rows had gone through nl_forward in ascending
+ * position order; rows of different streams are independent.  Rows [0, n_out) are OUTPUT rows: logits_out (may be NULL,
+ * n_out x vocab) and next_ids (may be NULL, n_out greedy argmax ids) are theirs; the other rows only write K / V.
+ * 0 <= n_out <= n, n_out <= 64, n <= nl_mixed_capacity's max_rows.  The rows of one stream are one run of distinct
+ * positions p0 .. p0+k-1, in ascending order among the output rows and among the other rows (not necessarily adjacent;
+ * the final prompt token, an output row, sits in front of the chunk that ends below it); anything else is
+ * NL_ERR_INVALID, checked before anything is queued.  A run that starts above the stream's high-water mark first clears the rows in between.
+ * Prompt chunks belong behind the output rows, each as adjacent rows: those attend on the segment-tile kernel, which
+ * fetches a chunk of K / V once per tile of queries (NL_MIXED_ATTN=0: every row on the per-token kernel).  A call in
+ * which no stream repeats and n_out == n IS nl_forward_batch, bit for bit.  Device groups: NL_ERR_UNSUPPORTED. */
+NL_API int nl_forward_mixed(nl_handle h, const int *streams, const int *tokens, const int *pos, int n, int n_out,
+                            float *logits_out, int *next_ids);
+/* The same step followed by the sampler of nl_forward_batch_sample on the n_out output rows (params, uniforms, recent
+ * windows, n_recent, next_ids all have n_out entries). */
+NL_API int nl_forward_mixed_sample(nl_handle h, const int *streams, const int *tokens, const int *pos, int n, int n_out,
+                                   const nl_sample_params *params, const float *uniforms,
+                                   int *recent, int recent_stride, int *n_recent, int *next_ids);
+/* Largest n and n_out the handle takes (after nl_finalize). */
+NL_API int nl_mixed_capacity(nl_handle h, int *max_rows, int *max_out);
 
 /* == introspection / measurement ========================================== */
 NL_API int nl_get_config(nl_handle h, nl_config *out); /* effective config (after seq_len cap etc.) */

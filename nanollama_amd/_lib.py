@@ -91,7 +91,8 @@ EXPORTS = ["nl_build_info", "nl_set_gamma", "nl_abi_version", "nl_device_count",
            "nl_memory_usage", "nl_debug_read", "nl_op_matmul", "nl_op_matmul_batch", "nl_op_rmsnorm", "nl_comm_get_unique_id",
            "nl_comm_init", "nl_group_forward", "nl_debug_stamps", "nl_sample_decode", "nl_op_sample", "nl_p2p_export",
            "nl_p2p_import", "nl_p2p_info", "nl_p2p_loopback", "nl_op_exp", "nl_plan_info", "nl_persist_info", "nl_create_group", "nl_host_logits",
-           "nl_op_gran16_soak", "nl_forward_batch_sample", "nl_op_sample_rows"]
+           "nl_op_gran16_soak", "nl_forward_batch_sample", "nl_op_sample_rows", "nl_forward_mixed", "nl_forward_mixed_sample",
+           "nl_mixed_capacity"]
 
 
 def lib():
@@ -149,6 +150,9 @@ def lib():
     L.nl_op_sample.argtypes = [i32, fp, i32, C.POINTER(NlSampleParams), C.c_float, ip, ip, ip]
     L.nl_forward_batch_sample.argtypes = [vp, ip, ip, ip, i32, C.POINTER(NlSampleParams), fp, ip, i32, ip, ip]
     L.nl_op_sample_rows.argtypes = [i32, fp, i32, i32, C.POINTER(NlSampleParams), fp, ip, i32, ip, ip]
+    L.nl_forward_mixed.argtypes = [vp, ip, ip, ip, i32, i32, fp, ip]
+    L.nl_forward_mixed_sample.argtypes = [vp, ip, ip, ip, i32, i32, C.POINTER(NlSampleParams), fp, ip, i32, ip, ip]
+    L.nl_mixed_capacity.argtypes = [vp, ip, ip]
     _lib = L
     return L
 

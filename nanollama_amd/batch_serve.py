@@ -12,7 +12,14 @@ thread owns the model handle (single-caller) and runs a loop of steps; every ste
      each end the request.
 
 A finished request gets its text and frees its stream; a request that arrives meanwhile joins at the next step.  Settings
-per request follow go/serve.go:94-103 (temperature, max_tokens and top_k come from the request when > 0); top_p,
+With prefill_chunk = N > 0 (--prefill-chunk) admission no longer runs the prompt: it only resets the stream and seeds the
+request's generator, and every step is ONE forward_mixed_sample call (nl_forward_mixed_sample) -- the decoding requests as
+output rows, then up to N prompt tokens of the admitted requests in admission order.  A prompt may span several steps and
+several short prompts may share one step's budget; in the step that feeds the last of a request's tokens 0 .. n_prompt - 2
+its final prompt token joins as an output row (it does not count against N) and the request decodes from then on.  The
+requests that are already decoding get a token in every step instead of waiting for whole prompts.
+
+Settings per request follow go/serve.go:94-103 (temperature, max_tokens and top_k come from the request when > 0); top_p,
 rep_penalty and rep_window are the server's.  Each request samples from its own generator, seeded from the scheduler's
 (seeded by --seed) in admission order, and draws a uniform only while its temperature is > 0, as Engine does.
 """
@@ -20,6 +27,7 @@ from __future__ import annotations
 
 import collections
 import threading
+import time
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -60,24 +68,36 @@ class _Row:
     out: TextOutput
     recent: List[int] = field(default_factory=list)
     n_out: int = 0           # ids sampled so far (EOS included)
+    pre: int = 0             # prefill_chunk > 0: prompt tokens (0 .. n_prompt - 2) to feed before the row decodes ...
+    fed: int = 0             # ... and how many of them have been fed
 
 
 class BatchScheduler:
     def __init__(self, model, tokenizer, parallel: int, rep_penalty: float = 1.15, rep_window: int = 64,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, prefill_chunk: int = 0):
         if not 1 <= parallel <= min(MAX_PARALLEL, model.max_streams):
             raise ValueError(f"parallel must be in [1, {min(MAX_PARALLEL, model.max_streams)}] (the handle's max_streams)")
         if model.config.vocab_size > MAX_VOCAB:
             raise ValueError(f"batched sampling covers vocabularies up to {MAX_VOCAB}, not {model.config.vocab_size}")
         if not 0 <= rep_window <= 1024:
             raise ValueError("rep_window must be in [0, 1024] for batched sampling")
+        if prefill_chunk < 0:
+            raise ValueError("prefill_chunk must be >= 0")
+        if prefill_chunk > 0:
+            max_rows = model.mixed_capacity[0]
+            if parallel + prefill_chunk > max_rows:
+                raise ValueError(f"parallel + prefill_chunk = {parallel + prefill_chunk} exceeds the {max_rows} rows of one "
+                                 f"mixed step (prefill_chunk <= {max_rows - parallel} with parallel {parallel})")
+        self.prefill_chunk = int(prefill_chunk)
+        self.max_step_gap_ms = 0.0                      # longest interval between two consecutive steps that both carried a decoding row
+        self._last_decode_step = None
         self.model, self.tokenizer = model, tokenizer
         self.parallel = parallel
         self.eos_id = tokenizer.eos_id
         self.rep_penalty = float(np.float32(rep_penalty))
         self.rep_window = int(rep_window)
         self.rng = np.random.default_rng(seed)
-        self.steps = 0                                  # forward_batch_sample calls so far
+        self.steps = 0                                  # forward_batch_sample / forward_mixed_sample calls so far
         self._cv = threading.Condition()
         self._queue: collections.deque = collections.deque()
         self._closed = False
@@ -130,32 +150,28 @@ class BatchScheduler:
             return
         try:
             self.model.reset(stream)
-            if n_prompt > 1:
+            if n_prompt > 1 and not self.prefill_chunk:
                 self.model.prefill(req.tokens[:n_prompt - 1], pos0=0, stream=stream, want_logits=False)
         except Exception as exc:                        # engine error: this request fails, the scheduler goes on
             free.append(stream)
             self._fail(req, 500, exc)
             return
+        if self.prefill_chunk:
+            row.pre = n_prompt - 1
         active.append(row)
 
-    def _step(self, active: List[_Row], free: List[int]) -> None:
+    def _note_step(self, decoding: bool) -> None:
+        """max_step_gap_ms: called when a step returns; `decoding`: it carried a row of a request that was already decoding."""
+        now = time.perf_counter()
+        if decoding and self._last_decode_step is not None:
+            self.max_step_gap_ms = max(self.max_step_gap_ms, (now - self._last_decode_step) * 1e3)
+        self._last_decode_step = now if decoding else None
+
+    def _apply(self, rows: List[_Row], ids, recents, free: List[int]) -> List[_Row]:
+        """The stop rules of Engine.generate_ids on the sampled rows; returns the ones that go on."""
         seq_len = self.model.config.seq_len
-        params = [dict(temperature=r.req.params.temperature, top_p=r.req.params.top_p, top_k=max(r.req.params.top_k, 1),
-                       rep_penalty=self.rep_penalty, rep_window=self.rep_window) for r in active]
-        uniforms = [r.rng.random(dtype=np.float32) if r.req.params.temperature > 0 else np.float32(0) for r in active]
-        try:
-            ids, recents = self.model.forward_batch_sample([r.stream for r in active], [r.token for r in active],
-                                                           [r.pos for r in active], params, uniforms,
-                                                           [r.recent for r in active])
-        except Exception as exc:                        # engine error: the requests of this call fail, the scheduler goes on
-            for r in active:
-                free.append(r.stream)
-                self._fail(r.req, 500, exc)
-            active.clear()
-            return
-        self.steps += 1
         keep = []
-        for r, t, rec in zip(active, ids, recents):
+        for r, t, rec in zip(rows, ids, recents):
             r.recent, r.n_out = rec, r.n_out + 1
             if t == self.eos_id:                        # go/main.go:203: not emitted
                 self._finish(r, free)
@@ -168,7 +184,67 @@ class BatchScheduler:
                 self._finish(r, free)
             else:
                 keep.append(r)
-        active[:] = keep
+        return keep
+
+    def _settings(self, rows: List[_Row]):
+        params = [dict(temperature=r.req.params.temperature, top_p=r.req.params.top_p, top_k=max(r.req.params.top_k, 1),
+                       rep_penalty=self.rep_penalty, rep_window=self.rep_window) for r in rows]
+        uniforms = [r.rng.random(dtype=np.float32) if r.req.params.temperature > 0 else np.float32(0) for r in rows]
+        return params, uniforms
+
+    def _step_mixed(self, active: List[_Row], free: List[int]) -> None:
+        """prefill_chunk > 0: one forward_mixed_sample call.  A row of `active` with fed < pre is still being admitted."""
+        decoding = [r for r in active if r.fed >= r.pre]
+        out_rows, chunks, touched, budget = list(decoding), [], [], self.prefill_chunk
+        for r in active:                                # admission order
+            if r.fed >= r.pre or budget == 0:
+                continue
+            take = min(r.pre - r.fed, budget)
+            chunks.append((r, r.fed, take))
+            touched.append(r)
+            budget -= take
+            if r.fed + take == r.pre:                   # its last chunk: the final prompt token samples in this step
+                out_rows.append(r)
+        streams = [r.stream for r in out_rows] + [r.stream for r, p0, k in chunks for _ in range(k)]
+        tokens = [r.token for r in out_rows] + [r.req.tokens[p] for r, p0, k in chunks for p in range(p0, p0 + k)]
+        pos = [r.pos for r in out_rows] + [p for r, p0, k in chunks for p in range(p0, p0 + k)]
+        params, uniforms = self._settings(out_rows)
+        try:
+            ids, recents = self.model.forward_mixed_sample(streams, tokens, pos, len(out_rows), params, uniforms,
+                                                           [r.recent for r in out_rows])
+        except Exception as exc:                        # engine error: the requests of this call fail, the scheduler goes on
+            failed = {id(r) for r in out_rows + touched}
+            for r in active:
+                if id(r) in failed:
+                    free.append(r.stream)
+                    self._fail(r.req, 500, exc)
+            active[:] = [r for r in active if id(r) not in failed]
+            self._last_decode_step = None
+            return
+        self.steps += 1
+        self._note_step(bool(decoding))
+        for r, p0, k in chunks:
+            r.fed = p0 + k
+        kept = {id(r) for r in self._apply(out_rows, ids, recents, free)}
+        sampled = {id(r) for r in out_rows}
+        active[:] = [r for r in active if id(r) in kept or id(r) not in sampled]
+
+    def _step(self, active: List[_Row], free: List[int]) -> None:
+        params, uniforms = self._settings(active)
+        try:
+            ids, recents = self.model.forward_batch_sample([r.stream for r in active], [r.token for r in active],
+                                                           [r.pos for r in active], params, uniforms,
+                                                           [r.recent for r in active])
+        except Exception as exc:                        # engine error: the requests of this call fail, the scheduler goes on
+            for r in active:
+                free.append(r.stream)
+                self._fail(r.req, 500, exc)
+            active.clear()
+            self._last_decode_step = None
+            return
+        self.steps += 1
+        self._note_step(True)
+        active[:] = self._apply(active, ids, recents, free)
 
     def _run(self) -> None:
         free = list(range(self.parallel))
@@ -186,7 +262,11 @@ class BatchScheduler:
                     admit.append((self._queue.popleft(), free.pop(0)))
             for req, stream in admit:
                 self._admit(req, stream, active, free)
-            if active:
+            if active and self.prefill_chunk:
+                self._step_mixed(active, free)
+            elif active:
                 self._step(active, free)
+            if not active:
+                self._last_decode_step = None           # (idle until the next request: not a gap between steps)
         for req in pending:
             self._fail(req, 500, RuntimeError("scheduler closed"))

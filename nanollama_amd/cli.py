@@ -3,6 +3,7 @@
     python -m nanollama_amd --model m.gguf --prompt "Hello"            (one shot)
     python -m nanollama_amd --model m.gguf --interactive               (REPL, /quit /exit /info)
     python -m nanollama_amd --model m.gguf --serve --port 8080         (HTTP: GET /, POST /chat, GET /health)
+    python -m nanollama_amd --model m.gguf --serve --parallel 16 --prefill-chunk 64   (batched server, chunked admission)
 """
 from __future__ import annotations
 
@@ -40,7 +41,25 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--parallel", type=int, default=1,
                     help="with --serve: decode up to N concurrent /chat requests as one sampled batch (N <= 64; "
                          "1 = one request at a time, as the reference)")
+    ap.add_argument("--prefill-chunk", type=int, default=0,
+                    help="with --serve --parallel N: admit prompts in chunks of up to this many tokens that share a step with "
+                         "the decoding requests (mixed steps) instead of running each prompt whole while the others wait; "
+                         "0 = whole prompts at admission")
     return ap
+
+
+MAX_MIXED_ROWS = 512         # rows of one mixed step (nl_mixed_capacity reports the handle's own limit, at most this)
+
+
+def check_prefill_chunk(args, max_rows: int = MAX_MIXED_ROWS) -> None:
+    """--prefill-chunk: needs the batched server, and parallel + chunk rows must fit one mixed step of the handle."""
+    if args.prefill_chunk < 0:
+        raise RuntimeError("--prefill-chunk must be >= 0")
+    if args.prefill_chunk > 0 and not batched(args):
+        raise RuntimeError("--prefill-chunk needs --serve --parallel N with N > 1")
+    if args.prefill_chunk > 0 and args.parallel + args.prefill_chunk > max_rows:
+        raise RuntimeError(f"--parallel {args.parallel} + --prefill-chunk {args.prefill_chunk} exceeds the {max_rows} rows of one "
+                           f"mixed step: --prefill-chunk <= {max_rows - args.parallel}")
 
 
 def check_parallel(args) -> None:
@@ -139,7 +158,10 @@ def main(argv=None) -> int:
             list_tensors(load_gguf(args.model, verbose=True))
             return 0
         check_parallel(args)
+        check_prefill_chunk(args)
         eng = load_engine(args)
+        if args.prefill_chunk > 0:
+            check_prefill_chunk(args, eng.model.mixed_capacity[0])
     except (GGUFError, OSError, RuntimeError, ImportError) as exc:
         print(f"error: {exc}", file=sys.stderr)
         return 1
@@ -149,8 +171,9 @@ def main(argv=None) -> int:
         if batched(args):
             from .batch_serve import BatchScheduler
             sched = BatchScheduler(eng.model, eng.tokenizer, args.parallel, rep_penalty=args.rep_penalty,
-                                   rep_window=args.rep_window, seed=args.seed)
-            print(f"[nanollama] continuous batching: up to {args.parallel} requests per decode step")
+                                   rep_window=args.rep_window, seed=args.seed, prefill_chunk=args.prefill_chunk)
+            print(f"[nanollama] continuous batching: up to {args.parallel} requests per decode step" +
+                  (f", prompts admitted in chunks of {args.prefill_chunk} tokens" if args.prefill_chunk else ""))
             try:
                 run_server(sched, params, args.port)
             finally:

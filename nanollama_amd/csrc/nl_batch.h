@@ -604,8 +604,10 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// The tile itself, shared by the two launch shapes below: items [i0, min(i0 + QT, n_items)) of stream `strm`, kv head kvh,
+// the keys of 128-position split `split`.
 template <int HD, int G, int QT>
-__global__ void __launch_bounds__(QT * G * 4, 2) attn_tile_kernel(AttnParams P, int n_items) {
+__device__ __forceinline__ void attn_tile_body(const AttnParams &P, const int n_items, const int kvh, const int split, const int i0, const int strm) {
     constexpr int VH = QT * G;               // rows (token, query head) per workgroup
     static_assert(VH % 16 == 0 && VH <= 64, "16 rows per wavefront");
     constexpr int NTH = VH * 4;              // threads: one wavefront per 16 rows
@@ -617,7 +619,7 @@ __global__ void __launch_bounds__(QT * G * 4, 2) attn_tile_kernel(AttnParams P, 
     __shared__ __attribute__((aligned(16))) float Vs[ATT_CH * HD];
     __shared__ int nv[VH];
 
-    const int kvh = blockIdx.x, split = blockIdx.y, i0 = blockIdx.z * QT, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int t0 = split * ATT_CH;
     int maxpos = -1;
     for (int i = 0; i < QT; i++)
@@ -643,7 +645,7 @@ __global__ void __launch_bounds__(QT * G * 4, 2) attn_tile_kernel(AttnParams P, 
             for (int s = 0; s < DK; s++) qa[s] = 0.f;
         }
     }
-    const long long soff = (long long)P.bstream[i0] * P.kv_stream_stride;
+    const long long soff = (long long)strm * P.kv_stream_stride;
     const float4 *K4 = reinterpret_cast<const float4 *>(P.kcache + soff + ((long long)kvh * P.seq_len + t0) * HD);
     const float4 *V4 = reinterpret_cast<const float4 *>(P.vcache + soff + ((long long)kvh * P.seq_len + t0) * HD);
     // every global load of the staging pass is issued before the first LDS store (one memory latency, not NIT);
@@ -764,6 +766,29 @@ __global__ void __launch_bounds__(QT * G * 4, 2) attn_tile_kernel(AttnParams P, 
         P.part_ml[slot * 2] = m;
         P.part_ml[slot * 2 + 1] = l;
     }
+}
+
+// a prompt of one stream: grid (kv head, 128-position split, tile of QT tokens)
+template <int HD, int G, int QT>
+__global__ void __launch_bounds__(QT * G * 4, 2) attn_tile_kernel(AttnParams P, int n_items) {
+    attn_tile_body<HD, G, QT>(P, n_items, blockIdx.x, blockIdx.y, blockIdx.z * QT, P.bstream[blockIdx.z * QT]);
+}
+
+// Mixed steps (nl_forward_mixed): the rows of a step belong to several streams, and a stream's rows form SEGMENTS -- runs of
+// consecutive positions, the chunk of a prompt that is being admitted beside the decode rows of the running requests.  The host
+// lists the work of the segments that take this kernel, one entry per (query tile of up to QT rows of ONE segment, 128-key
+// chunk of that segment's stream): grid (kv head, entry).  An entry is two words, first row | rows << 16 and stream << 4 | chunk;
+// entries with no rows pad the list to the length the step's graph was captured with.  A workgroup stages its chunk of K / V
+// once for all the rows of its tile and the G query heads of the group -- the per-token kernel fetches it once per row -- and
+// masks by each row's own position, which covers the rows the Q|K|V launch of this very layer stored.  Partials leave per
+// (row, head, chunk) in attn_kernel's layout, so one battn_merge_kernel launch serves the whole step.  Full float32 products
+// on v_mfma_f32_16x16x4_f32, fixed reduction order.
+template <int HD, int G, int QT>
+__global__ void __launch_bounds__(QT * G * 4, 2) attn_seg_kernel(AttnParams P, const int2 *work) {
+    const int a = sload_i32(reinterpret_cast<const int *>(work + blockIdx.y)), b = sload_i32(reinterpret_cast<const int *>(work + blockIdx.y) + 1);
+    const int i0 = a & 0xFFFF, cnt = (int)((unsigned)a >> 16);
+    if (cnt == 0) return;
+    attn_tile_body<HD, G, QT>(P, i0 + cnt, blockIdx.x, b & 15, i0, (int)((unsigned)b >> 4));
 }
 
 // ---- the same tile on the fp16 matrix cores -------------------------------------------------------------

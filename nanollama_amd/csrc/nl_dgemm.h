@@ -709,7 +709,7 @@ inline bool dg_head_ok(int rows, int cols) {
 }
 template <int NWV, int NS>
 inline hipError_t dg_launch_head_k(QGemmParams P, hipStream_t st, int num_cus) {
-    P.nt16 = ((P.n_tokens + 63) / 64) * 4;
+    if (!P.nt16) P.nt16 = ((P.n_tokens + 63) / 64) * 4;     // (preset: a head over the first rows of a longer step's fragments)
     P.ksplit = 1;
     if constexpr (DgHeadLds<NWV, NS>::TOTAL_U4 * 16 <= DG_LDS_BYTES - 512) {
         const int ntt = (P.n_tokens + 15) / 16, nrg = (P.ntiles + DGH_T - 1) / DGH_T;

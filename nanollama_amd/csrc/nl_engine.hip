@@ -46,7 +46,7 @@ namespace {
 // ---- environment knobs (development, tests, tools) ----------------------------------------------------------------------------
 // Every NL_* variable the library reads is read here and nowhere else, at one of three points.  process: once, at the first use of
 // any (process_knobs()).  handle: in nl_create (nl_engine::knobs; nl_op_matmul's temporary engine: per call).  step: once per call
-// of nl_prefill / nl_forward_batch / nl_op_matmul_batch (StepKnobs): tests and bench.py flip them on a live handle, and a cached
+// of nl_prefill / nl_forward_batch / nl_forward_mixed / nl_op_matmul_batch (StepKnobs): tests and bench.py flip them on a live handle, and a cached
 // decode-batch step graph is keyed on all of them.  Values parse as atoi does (junk is 0); "set": present, whatever the value.
 //
 //   knob                          default     read     switches
@@ -106,6 +106,10 @@ namespace {
 //   NL_DGEMM                      1           step     0: multi-token steps keep the split-K / long-run GEMMs
 //   NL_DGEMM_MAX_TOKENS           by shape    step     longest step dgemm_kernel takes (dgemm_step_ok)
 //   NL_DGEMM_HEAD                 1           step     0: a decode batch's LM head stays bnorm + split-K + argmax
+//   NL_MIXED_ATTN                 1           step     0: every row of a mixed step (nl_forward_mixed) attends on the per-token kernel
+//   NL_MIXED_ATTN_MIN             512         step     (row, visible 128-key chunk) pairs of a mixed step's prompt segments from which
+//                                                      they take the segment-tile kernel (0: always; below it the second launch costs
+//                                                      more than the K / V fetches it saves)
 std::optional<int> knob_opt(const char *name) { const char *v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; }
 int knob_int(const char *name, int dflt) { return knob_opt(name).value_or(dflt); }
 bool knob_off(const char *name) { return knob_opt(name) == 0; }     // set and 0
@@ -152,7 +156,8 @@ struct StepKnobs {
     }();
     int qg2_min_tokens = knob_int("NL_QG2_MIN_TOKENS", 128), kv16_min_tokens = knob_int("NL_KV16_MIN_TOKENS", 256), att_run = knob_int("NL_ATT_RUN", 0);
     bool fold_norm = !knob_off("NL_FOLD_NORM"), rope_in_attn = !knob_off("NL_ROPE_IN_ATTN"), dgemm = !knob_off("NL_DGEMM"),
-         dgemm_head = !knob_off("NL_DGEMM_HEAD");
+         dgemm_head = !knob_off("NL_DGEMM_HEAD"), mixed_attn = !knob_off("NL_MIXED_ATTN");
+    int mixed_attn_min = knob_int("NL_MIXED_ATTN_MIN", 512);
     std::optional<int> dgemm_max_tokens = knob_opt("NL_DGEMM_MAX_TOKENS");
     bool operator==(const StepKnobs &) const = default;
     int x1_gemm() const { return prefill == Precision::fp16x1 || prefill == Precision::fp16x1_gemm; }
@@ -357,6 +362,9 @@ struct nl_engine {
     SampScratch bs;
     int *bs_dev = nullptr, *h_bs = nullptr;
     std::vector<StepGraph> bs_graphs;
+    // mixed steps (nl_forward_mixed / nl_forward_mixed_sample): step (+ sampler) graphs keyed on everything that shapes a launch
+    struct MixedGraph { int n, n_out, n_tok, n_work, ns_tok; bool sampled; StepKnobs knobs; hipGraph_t graph; hipGraphExec_t exec; };
+    std::vector<MixedGraph> mx_graphs;
 
     // on-device sampling (nl_sample_decode): scratch for one vocabulary, allocated on first use
     SampScratch sp;
@@ -637,6 +645,7 @@ hipError_t launch_attn_hd(int gqa, AttnParams P, dim3 grid, hipStream_t st) {
     case 2: hipLaunchKernelGGL((attn_kernel<HD, 2>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 3: hipLaunchKernelGGL((attn_kernel<HD, 3>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 4: hipLaunchKernelGGL((attn_kernel<HD, 4>), grid, dim3(ATT_THREADS), 0, st, P); break;
+    case 6: hipLaunchKernelGGL((attn_kernel<HD, 6>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 8: hipLaunchKernelGGL((attn_kernel<HD, 8>), grid, dim3(ATT_THREADS), 0, st, P); break;
     default: return hipErrorInvalidValue;
     }
@@ -650,6 +659,7 @@ hipError_t launch_attn_fin_hd(int gqa, AttnParams P, dim3 grid, hipStream_t st) 
     case 2: hipLaunchKernelGGL((attn_kernel<HD, 2, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 3: hipLaunchKernelGGL((attn_kernel<HD, 3, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 4: hipLaunchKernelGGL((attn_kernel<HD, 4, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
+    case 6: hipLaunchKernelGGL((attn_kernel<HD, 6, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 8: hipLaunchKernelGGL((attn_kernel<HD, 8, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     default: return hipErrorInvalidValue;
     }
@@ -664,6 +674,7 @@ hipError_t launch_attn_rope_hd(int gqa, AttnParams P, dim3 grid, hipStream_t st)
     case 2: hipLaunchKernelGGL((attn_kernel<HD, 2, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 3: hipLaunchKernelGGL((attn_kernel<HD, 3, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 4: hipLaunchKernelGGL((attn_kernel<HD, 4, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
+    case 6: hipLaunchKernelGGL((attn_kernel<HD, 6, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     case 8: hipLaunchKernelGGL((attn_kernel<HD, 8, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
     default: return hipErrorInvalidValue;
     }
@@ -688,6 +699,21 @@ void launch_attn_tile_g(const AttnParams &P, int n, int kvs, int nsplit, hipStre
         else hipLaunchKernelGGL((attn_tile16_kernel<HD, G, QT16, false>), dim3(kvs, nsplit, (n + QT16 - 1) / QT16), dim3(QT16 * G * 4), 0, st, P, n);
     }
 }
+// mixed steps: the segment-tile kernel over the host's work list (grid: kv head x entry)
+template <int HD>
+hipError_t launch_attn_seg_hd(int gqa, const AttnParams &P, const int2 *work, int kvs, int n_work, hipStream_t st) {
+    const dim3 grid(kvs, n_work);
+    switch (gqa) {
+    case 1: hipLaunchKernelGGL((attn_seg_kernel<HD, 1, AttnTileQT<1>::value>), grid, dim3(AttnTileQT<1>::value * 1 * 4), 0, st, P, work); break;
+    case 2: hipLaunchKernelGGL((attn_seg_kernel<HD, 2, AttnTileQT<2>::value>), grid, dim3(AttnTileQT<2>::value * 2 * 4), 0, st, P, work); break;
+    case 3: hipLaunchKernelGGL((attn_seg_kernel<HD, 3, AttnTileQT<3>::value>), grid, dim3(AttnTileQT<3>::value * 3 * 4), 0, st, P, work); break;
+    case 4: hipLaunchKernelGGL((attn_seg_kernel<HD, 4, AttnTileQT<4>::value>), grid, dim3(AttnTileQT<4>::value * 4 * 4), 0, st, P, work); break;
+    case 8: hipLaunchKernelGGL((attn_seg_kernel<HD, 8, AttnTileQT<8>::value>), grid, dim3(AttnTileQT<8>::value * 8 * 4), 0, st, P, work); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+inline int attn_tile_qt(int gqa) { return gqa == 1 ? 64 : gqa == 2 ? 32 : gqa == 8 ? 8 : 16; }   // = AttnTileQT<G>::value
 inline int attn_tile16_qt(int gqa) { return NL_ATT16_MUL * (gqa == 1 ? 64 : gqa == 2 ? 32 : gqa == 8 ? 8 : 16); }   // = AttnTile16QT<G>::value
 inline bool attn_tile_supported(int gqa) { return gqa == 1 || gqa == 2 || gqa == 3 || gqa == 4 || gqa == 8; }
 template <int HD>
@@ -2046,7 +2072,12 @@ hipError_t launch_qgemm_plain(nl_engine *e, nl_engine::Batch &bt, const PackedMa
 // One multi-token step: n <= 64 (token, pos, stream) triples through every layer on the MFMA path.
 // lm_mode: 0 = no LM head, 1 = logits + argmax for every token, 2 = logits + argmax for the LAST token only.
 // The caller has filled bt.h_meta; stream-ordered, no synchronisation inside.
-int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int lm_mode, const StepKnobs &k, bool one_stream = false) {
+// mx (nl_forward_mixed): a stream may own several rows.  The LM head of lm_mode 1 covers rows [0, n_out) only; rows [0, n_tok)
+// attend on the per-token kernel, the rest through the n_work entries of the segment work list the caller left in h_meta
+// (attn_seg_kernel, nl_batch.h); the Q|K|V launch of a layer stores every row's K / V before any row of the layer attends.
+struct MixedPlan { int n_out, n_tok, n_work; };
+int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int lm_mode, const StepKnobs &k, bool one_stream = false,
+                 const MixedPlan *mx = nullptr) {
     const nl_config &c = e->cfg;
     const int D = c.dim, hd = e->hd, HQ = e->Hs * hd, R = (e->Hs + 2 * e->KVs) * hd;
 #define LCK(expr) do { hipError_t s_ = (expr); if (s_ != hipSuccess) return e->fail(NL_ERR_HIP, "batched step: %s: %s", #expr, hipGetErrorString(s_)); } while (0)
@@ -2108,7 +2139,9 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     for (int i = 1; i < n && consecutive; i++) consecutive = b.h_meta[b.cap + i] == b.h_meta[b.cap] + i;
     nsplit = std::min(nsplit, e->nsplit_max);
     const bool tile_attn = one_stream && n >= 8 && attn_tile_supported(e->gqa) && !no_tile;   // prompts: attn_tile16_kernel
-    const bool fin_attn = !tile_attn && nsplit == 1 && !no_fin;                                 // one split: attn_kernel<..., FIN>
+    const bool fin_attn = !tile_attn && nsplit == 1 && !no_fin && !mx;                          // one split: attn_kernel<..., FIN>
+    const int lm_rows = mx ? mx->n_out : n;      // rows of an lm_mode 1 head
+    if (mx && lm_rows == 0) lm_mode = 0;
     GemmOut pend{nullptr, nullptr, 1, 0, nullptr};   // GEMM output not yet folded into the residual stream
     // RMSNorm folded around the GEMMs (QGemmParams::NormOut / NormIn): when WO and down run unsplit on qgemm2_kernel and
     // their consumers are the fused-epilogue GEMMs of the same kernel -- a Q4_0 prompt -- the producing GEMM writes the
@@ -2117,7 +2150,7 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     // reads xfrag2, everything else xfrag.
     const bool dg = dgemm_step_ok(e, n, k);      // short token runs (decode batches): nl_dgemm.h, always folded
     // ... and the LM head of a step that wants every token's logits (NL_DGEMM_HEAD=0: the split-K launches)
-    const bool dg_head = dg && lm_mode == 1 && e->dg_head && n <= b.lm_cap && (size_t)n * e->lm_head.ntiles * 2 <= b.kpart_cap && k.dgemm_head;
+    const bool dg_head = dg && lm_mode == 1 && e->dg_head && lm_rows <= b.lm_cap && (size_t)lm_rows * e->lm_head.ntiles * 2 <= b.kpart_cap && k.dgemm_head;
     bool fold = k.fold_norm && !c.qk_norm && D % 64 == 0 && c.n_layers > 0;
     for (int l = 0; l < c.n_layers && fold; l++) {
         const nl_engine::Layer &L = e->layers[l];
@@ -2168,7 +2201,8 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             // Below position 128 that is the one-split FIN kernel; with two splits per token every split rotates q and the
             // last one k / v.  Beyond that the repeated q work of every split costs more than the launch it saves (goldie x
             // 64 streams: positions 130..145 2.03 -> 1.92 ms per step, 300.. 2.19 -> 2.19, 1000.. 2.85 -> 2.95).
-            rope_in_attn = !tile_attn && nsplit <= 2 && !one_stream && !c.qk_norm && k.rope_in_attn;
+            // (not a mixed step: there a row does attend over rows this step stores)
+            rope_in_attn = !tile_attn && nsplit <= 2 && !one_stream && !mx && !c.qk_norm && k.rope_in_attn;
             if (!rope_in_attn) {
                 const GemmOut &qkv = qkv_out;
                 BRopeParams P{qkv, R, hd, e->Hs, e->KVs, c.seq_len, c.rope_conjugate, c.qk_norm, c.rms_eps, b.pos, b.stream,
@@ -2185,7 +2219,18 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
                          (float)(1.0 / std::sqrt((double)hd)), 0, b.pos, b.stream, (long long)HQ,
                          (long long)e->Hs * e->nsplit_max};
             bool merged = false;
-            if (one_stream && n >= 8 && attn_tile_supported(e->gqa) && !no_tile) {
+            if (mx) {
+                // rows [0, n_tok): decode rows and whatever else the work list does not cover, one workgroup per (kv head, split,
+                // row); the prompt segments behind them: one per (kv head, query tile, chunk)
+                int ns_tok = 1;
+                for (int i = 0; i < mx->n_tok; i++) ns_tok = std::max(ns_tok, b.h_meta[b.cap + i] / ATT_CH + 1);
+                if (mx->n_tok > 0) LCK(launch_attn(hd, e->gqa, P, dim3(e->KVs, std::min(ns_tok, e->nsplit_max), mx->n_tok), st));
+                if (mx->n_work > 0) {
+                    const int2 *work = reinterpret_cast<const int2 *>(b.tok + 3 * b.cap);
+                    LCK(hd == 64 ? launch_attn_seg_hd<64>(e->gqa, P, work, e->KVs, mx->n_work, st)
+                                 : launch_attn_seg_hd<32>(e->gqa, P, work, e->KVs, mx->n_work, st));
+                }
+            } else if (one_stream && n >= 8 && attn_tile_supported(e->gqa) && !no_tile) {
                 // prefill: the step's tokens share a stream -> K/V split staged once per tile of tokens, fp16 MFMA with hi/lo-split operands (attn_tile16_kernel)
                 AttnParams T = P;
                 T.x1 = k.x1_attn();
@@ -2296,7 +2341,7 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     }
     if (lm_mode) {
         // logits rows [0, cnt) of bt.logits / ids [0, cnt): all tokens (mode 1, n <= lm_cap) or just the last (mode 2)
-        const int first = lm_mode == 2 ? n - 1 : 0, cnt = lm_mode == 2 ? 1 : n;
+        const int first = lm_mode == 2 ? n - 1 : 0, cnt = lm_mode == 2 ? 1 : lm_rows;
         if (cnt > b.lm_cap) return e->fail(NL_ERR_INVALID, "LM head batch %d exceeds %d", cnt, b.lm_cap);
         if (dg_head) {
             // final RMSNorm folded (the last down launch wrote the fragments and sums of squares), logits + one argmax candidate
@@ -2304,9 +2349,10 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
             const PackedMat &m = e->lm_head;
             QGemmParams P{};
             P.q = m.q3; P.s = m.s3; P.rows = m.rows; P.cols = m.cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
-            P.xf = b.xfrag2; P.nrm_in = nin_attn; P.n_tokens = n; P.out = b.logits; P.ldo = c.vocab; P.part1 = b.kpart;
+            P.xf = b.xfrag2; P.nrm_in = nin_attn; P.n_tokens = lm_rows; P.out = b.logits; P.ldo = c.vocab; P.part1 = b.kpart;
+            P.nt16 = nt16;      // (the fragments were stored for all n rows of the step)
             LCK(launch_dgemm_head(P, st, e->num_cus));
-            hipLaunchKernelGGL(dg_argmax_kernel, dim3(n), dim3(1024), 0, st, reinterpret_cast<const uint2 *>(b.kpart), m.ntiles, b.ids);
+            hipLaunchKernelGGL(dg_argmax_kernel, dim3(lm_rows), dim3(1024), 0, st, reinterpret_cast<const uint2 *>(b.kpart), m.ntiles, b.ids);
         } else {
             LCK(norm(e->output_norm, e->lm_head, first, cnt));
             LCK(launch_qgemm_plain(e, b, e->lm_head, cnt, b.logits, c.vocab, k, st));
@@ -2355,6 +2401,8 @@ void destroy_step_graphs(nl_engine *e) {
     auto drop = [](std::vector<nl_engine::StepGraph> &gs) { for (auto &G : gs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); } gs.clear(); };
     drop(e->bt_graphs);
     drop(e->bs_graphs);
+    for (auto &G : e->mx_graphs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); }
+    e->mx_graphs.clear();
     for (auto &sb : e->sub) drop(sb.graphs);
 }
 
@@ -2504,7 +2552,8 @@ int nl_create(const nl_config *cfg, nl_handle *out) {
     if (c.dim % 32 || c.interm % 32) return bad("config: dim and interm must be multiples of 32 (whole quant blocks)");
     if (c.head_dim != 32 && c.head_dim != 64) { g_create_error = "head_dim must be 32 or 64 on this build"; return NL_ERR_UNSUPPORTED; }
     int gq = c.n_heads / c.n_kv_heads;
-    if (gq != 1 && gq != 2 && gq != 3 && gq != 4 && gq != 8) { g_create_error = "GQA group size must be 1,2,3,4 or 8"; return NL_ERR_UNSUPPORTED; }
+    // (6: the per-token attention kernel and the general five-launch plan only -- no tile kernels, no fused plans)
+    if (gq != 1 && gq != 2 && gq != 3 && gq != 4 && gq != 6 && gq != 8) { g_create_error = "GQA group size must be 1,2,3,4,6 or 8"; return NL_ERR_UNSUPPORTED; }
     if (c.tp_rank < 0 || c.tp_rank >= c.tp_size) return bad("config: tp_rank out of range");
     if (c.n_heads % c.tp_size || c.n_kv_heads % c.tp_size || c.vocab % c.tp_size || c.interm % (32 * c.tp_size))
         return bad("config: heads / kv heads / vocab / interm(32-blocks) must divide by tp_size");
@@ -3030,6 +3079,7 @@ int nl_finalize(nl_handle e) {
             }
         }
         e->fused_mode = ok1 ? 1 : ok3 ? 3 : ok4 ? 4 : ok2 ? 2 : 0;
+        if (!attn_tile_supported(e->gqa)) e->fused_mode = 0;      // (a GQA factor the fused launches were never run with: the general plan)
         e->fused = e->fused_mode != 0;
         if (e->fused_mode != 3) e->wide_ffn = e->fused_mode == 4 && wide_ffn_ok();     // the feed-forward half as one launch too
         // tools/fused_limit.py: the per-head blocks (mode 1) win up to ~500 (nano) / ~600 (mini) positions, the projection +
@@ -3840,6 +3890,17 @@ hipError_t launch_block_sample(const SampScratch &s, int vocab, int *blk, int m,
     return launch_sample_kernels(P, nrows, modes, st);
 }
 
+// the sampler's scratch and the call's block, once per handle
+int bs_prepare(nl_engine *e) {
+    if (e->h_bs) return NL_OK;
+    std::lock_guard<std::mutex> setup(g_setup_mu);
+    const size_t words = bs_layout(BS_MAX_ROWS).total;
+    HIPCK(e, samp_alloc(e->bs, e->cfg.vocab, 1, BS_MAX_ROWS, &e->bytes_state));
+    HIPCK(e, dalloc(&e->bs_dev, words, &e->bytes_state));
+    HIPCK(e, hipHostMalloc((void **)&e->h_bs, words * 4, hipHostMallocDefault));
+    return NL_OK;
+}
+
 }  // namespace
 
 int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, const int *pos, int n,
@@ -3866,13 +3927,7 @@ int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, 
     if (n == 0) return NL_OK;
     HIPCK(e, hipSetDevice(e->dev));
     if (int qrc = pd_session_close(e)) return qrc;
-    if (!e->h_bs) {
-        std::lock_guard<std::mutex> setup(g_setup_mu);
-        const size_t words = bs_layout(BS_MAX_ROWS).total;
-        HIPCK(e, samp_alloc(e->bs, e->cfg.vocab, 1, BS_MAX_ROWS, &e->bytes_state));
-        HIPCK(e, dalloc(&e->bs_dev, words, &e->bytes_state));
-        HIPCK(e, hipHostMalloc((void **)&e->h_bs, words * 4, hipHostMallocDefault));
-    }
+    if ((rc = bs_prepare(e))) return rc;
     for (int i = 0; i < n; i++)
         if ((rc = note_positions(e, streams[i], pos[i], 1))) return rc;
     // every call brings its settings, uniforms and windows again: nothing but KV rows and position marks outlives it
@@ -3952,6 +4007,226 @@ int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, 
         n_recent[i] = h[L.nrec + i];
         memcpy(recent + (size_t)i * recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)n_recent[i] * 4);
     }
+    return NL_OK;
+}
+
+namespace {
+
+constexpr int MX_MAX_ROWS = 512;      // rows of one mixed step
+constexpr int MX_MAX_GRAPHS = 64;     // cached mixed-step graphs per handle; further geometries run eagerly
+
+int mixed_max_rows(const nl_engine *e) {     // min(MX_MAX_ROWS, Batch::cap) without allocating the step buffers (batch_alloc)
+    return std::min(MX_MAX_ROWS, ((e->cfg.seq_len + QG_TOK - 1) / QG_TOK) * QG_TOK);
+}
+
+struct MixedSample { const nl_sample_params *params; const float *uniforms; int *recent; int recent_stride; int *n_recent; };
+
+// nl_forward_mixed / nl_forward_mixed_sample (sm != null)
+int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, int n_out, float *logits_out,
+                  int *next_ids, const MixedSample *sm) {
+    const char *const who = sm ? "nl_forward_mixed_sample" : "nl_forward_mixed";
+    if (!e) return NL_ERR_INVALID;
+    if (e->grp) return e->fail(NL_ERR_UNSUPPORTED, "%s: device groups are not supported", who);
+    if (!streams || !tokens || !pos || n < 0) return e->fail(NL_ERR_INVALID, "%s: null argument or negative row count", who);
+    if (sm && n_out > 0 && (!sm->params || !sm->uniforms || !sm->recent || !sm->n_recent || !next_ids))
+        return e->fail(NL_ERR_INVALID, "%s: null sampler argument", who);
+    if (!e->finalized) return e->fail(NL_ERR_STATE, "forward before nl_finalize");
+    if (n_out < 0 || n_out > n) return e->fail(NL_ERR_INVALID, "%s: n_out %d outside [0, n = %d]", who, n_out, n);
+    if (n_out > BS_MAX_ROWS) return e->fail(NL_ERR_INVALID, "%s: n_out %d exceeds the LM head's batch of %d rows", who, n_out, BS_MAX_ROWS);
+    if (n > mixed_max_rows(e)) return e->fail(NL_ERR_INVALID, "%s: step of %d rows exceeds %d", who, n, mixed_max_rows(e));
+    if (sm && e->cfg.vocab > 131072) return e->fail(NL_ERR_UNSUPPORTED, "on-device sampling covers vocabularies up to 131072, not %d", e->cfg.vocab);
+    int rc;
+    // per stream: one gap-free run of distinct positions, ascending among the output rows and among the other rows (an output
+    // row sits in front of the chunk that ends just below it: the two parts of the arrays are ordered each on its own)
+    struct Run { int stream, lo, hi, k, last[2]; };
+    std::vector<Run> runs;
+    bool repeats = false;
+    for (int i = 0; i < n; i++) {
+        if ((rc = check_step_args(e, streams[i], tokens[i], pos[i]))) return rc;
+        const int part = i < n_out ? 0 : 1;
+        size_t r = 0;
+        while (r < runs.size() && runs[r].stream != streams[i]) r++;
+        if (r == runs.size()) runs.push_back({streams[i], pos[i], pos[i], 0, {-1, -1}});
+        else repeats = true;
+        Run &R = runs[r];
+        if (pos[i] <= R.last[part])
+            return e->fail(NL_ERR_INVALID, "%s: stream %d: row %d at position %d follows position %d (the rows of a stream ascend)",
+                           who, streams[i], i, pos[i], R.last[part]);
+        R.last[part] = pos[i];
+        R.lo = std::min(R.lo, pos[i]); R.hi = std::max(R.hi, pos[i]); R.k++;
+    }
+    for (int i = 0; repeats && i < n_out; i++)
+        for (int j = n_out; j < n; j++)
+            if (streams[i] == streams[j] && pos[i] == pos[j])
+                return e->fail(NL_ERR_INVALID, "%s: stream %d: position %d appears twice (rows %d and %d)", who, streams[i], pos[i], i, j);
+    for (const Run &R : runs)
+        if (R.hi - R.lo + 1 != R.k)
+            return e->fail(NL_ERR_INVALID, "%s: stream %d: %d rows over positions %d..%d (the rows of a stream are one run without gaps)",
+                           who, R.stream, R.k, R.lo, R.hi);
+    for (int i = 0; sm && i < n_out; i++) {
+        if ((rc = check_sample_params(e, &sm->params[i]))) return rc;
+        if (sm->params[i].rep_window > sm->recent_stride)
+            return e->fail(NL_ERR_INVALID, "rep_window %d of row %d exceeds recent_stride %d", sm->params[i].rep_window, i, sm->recent_stride);
+        if (sm->n_recent[i] < 0 || sm->n_recent[i] > sm->params[i].rep_window)
+            return e->fail(NL_ERR_INVALID, "n_recent %d of row %d exceeds rep_window %d", sm->n_recent[i], i, sm->params[i].rep_window);
+    }
+    if (n == 0) return NL_OK;
+    // a decode batch: the existing path, bit for bit
+    if (!repeats && n_out == n)
+        return sm ? nl_forward_batch_sample(e, streams, tokens, pos, n, sm->params, sm->uniforms, sm->recent, sm->recent_stride, sm->n_recent, next_ids)
+                  : nl_forward_batch(e, streams, tokens, pos, n, logits_out, next_ids);
+    HIPCK(e, hipSetDevice(e->dev));
+    if (int qrc = pd_session_close(e)) return qrc;
+    if (sm && n_out > 0 && (rc = bs_prepare(e))) return rc;
+    const StepKnobs k;
+    const bool multi = n >= process_knobs().batch_min && batch_supported(e);
+    if (multi) {
+        std::lock_guard<std::mutex> setup(g_setup_mu);
+        if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc;
+        if (n > e->bt.cap) return e->fail(NL_ERR_INVALID, "%s: step of %d rows exceeds %d", who, n, e->bt.cap);
+    }
+    for (const Run &r : runs)
+        if ((rc = note_positions(e, r.stream, r.lo, r.k))) return rc;
+    const size_t V = (size_t)e->cfg.vocab;
+    const BsLayout L = bs_layout(std::max(n_out, 1));
+    int *const h = e->h_bs;
+    auto pack = [&]() {
+        for (int i = 0; sm && i < n_out; i++) {
+            reinterpret_cast<SampRow *>(h + L.rows)[i] = samp_row_of(sm->params[i]);
+            reinterpret_cast<float *>(h + L.u)[i] = sm->uniforms[i];
+            h[L.nrec + i] = sm->n_recent[i];
+            memcpy(h + L.win + (size_t)i * SAMP_THREADS, sm->recent + (size_t)i * sm->recent_stride, (size_t)sm->n_recent[i] * 4);
+        }
+    };
+    const bool sampled = sm && n_out > 0;
+    if (multi) {
+        nl_engine::Batch &b = e->bt;
+        for (int i = 0; i < n; i++) {
+            b.h_meta[i] = tokens[i];
+            b.h_meta[b.cap + i] = pos[i];
+            b.h_meta[2 * b.cap + i] = streams[i];
+        }
+        // The attention plan.  Output rows and the single rows right behind them: the per-token kernel.  From there on every
+        // run of adjacent rows of one stream at consecutive positions is a segment, cut into query tiles; a tile and a
+        // 128-key chunk it can see make one entry of the work list (attn_seg_kernel, nl_batch.h).  The list lives where a
+        // prompt step keeps its workgroup list and partial counts: 2 * cap words, two per entry.  A step whose list does not
+        // fit, or whose segments are too small to pay for the second launch, keeps every row on the per-token kernel.
+        MixedPlan mp{n_out, n, 0};
+        if (k.mixed_attn && attn_tile_supported(e->gqa)) {
+            auto follows = [&](int i) { return i > n_out && streams[i] == streams[i - 1] && pos[i] == pos[i - 1] + 1; };
+            int n_tok = n_out;
+            while (n_tok < n && !follows(n_tok) && !(n_tok + 1 < n && follows(n_tok + 1))) n_tok++;
+            const int qt = attn_tile_qt(e->gqa);
+            int *work = b.h_meta + 3 * b.cap, nw = 0;
+            long long pairs = 0;      // (row, visible chunk) pairs of the segments: what the per-token kernel would fetch a chunk for
+            bool fits = true;
+            for (int s0 = n_tok; s0 < n && fits;) {
+                int s1 = s0 + 1;
+                while (s1 < n && follows(s1)) s1++;
+                for (int q0 = s0; q0 < s1 && fits; q0 += qt) {
+                    const int cnt = std::min(qt, s1 - q0), chunks = std::min(pos[q0 + cnt - 1] / ATT_CH + 1, e->nsplit_max);
+                    fits = nw + chunks <= b.cap - 8;
+                    pairs += (long long)cnt * chunks;
+                    for (int c = 0; c < chunks && fits; c++, nw++) {
+                        work[2 * nw] = q0 | (cnt << 16);
+                        work[2 * nw + 1] = (int)(((unsigned)streams[s0] << 4) | (unsigned)c);
+                    }
+                }
+                s0 = s1;
+            }
+            // (few pairs: the tile launch behind the per-token one costs more than the fetches it saves -- measured)
+            if (fits && nw > 0 && pairs >= k.mixed_attn_min) {
+                for (; nw % 8; nw++) work[2 * nw] = work[2 * nw + 1] = 0;     // (fewer distinct grids, i.e. graphs)
+                mp.n_tok = n_tok; mp.n_work = nw;
+            }
+        }
+        int ns_tok = 1;
+        for (int i = 0; i < mp.n_tok; i++) ns_tok = std::max(ns_tok, pos[i] / ATT_CH + 1);
+        pack();
+        auto body = [&](hipStream_t st) -> int {
+            if (sampled) HIPCK(e, hipMemcpyAsync(e->bs_dev, h, L.total * 4, hipMemcpyHostToDevice, st));
+            if (int r2 = batched_step(e, b, st, n, 1, k, false, &mp)) return r2;
+            if (sampled) {
+                HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n_out, 0, n_out, b.logits, 7u, st));
+                HIPCK(e, hipMemcpyAsync(h + L.nrec, e->bs_dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, st));
+            }
+            return NL_OK;
+        };
+        hipGraphExec_t exec = nullptr;
+        for (const auto &G : e->mx_graphs)
+            if (G.n == n && G.n_out == n_out && G.n_tok == mp.n_tok && G.n_work == mp.n_work && G.ns_tok == ns_tok && G.sampled == sampled && G.knobs == k)
+                exec = G.exec;
+        if (!exec && e->use_graph && (int)e->mx_graphs.size() < MX_MAX_GRAPHS) {
+            std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
+            hipGraph_t gr = nullptr;
+            if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                const int r2 = body(e->stream);
+                const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
+                if (!r2 && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess)
+                    e->mx_graphs.push_back({n, n_out, mp.n_tok, mp.n_work, ns_tok, sampled, k, gr, exec});
+                else { if (gr) (void)hipGraphDestroy(gr); exec = nullptr; }
+            }
+            (void)hipGetLastError();
+        }
+        if (exec) HIPCK(e, hipGraphLaunch(exec, e->stream));
+        else if ((rc = body(e->stream))) return rc;
+        if (logits_out && n_out > 0) HIPCK(e, hipMemcpyAsync(logits_out, b.logits, (size_t)n_out * V * 4, hipMemcpyDeviceToHost, e->stream));
+        if (!sm && next_ids && n_out > 0) HIPCK(e, hipMemcpyAsync(next_ids, b.ids, (size_t)n_out * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPCK(e, hipStreamSynchronize(e->stream));
+    } else {
+        // a format or a step outside the multi-token path: every row's single-token step in (stream, position) order, an output
+        // row's logits / argmax / sampler right behind its own step
+        std::vector<int> order((size_t)n);
+        for (int i = 0; i < n; i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int c2) { return streams[a] != streams[c2] ? streams[a] < streams[c2] : pos[a] < pos[c2]; });
+        for (int attempt = 0;; attempt++) {
+            pack();
+            if (sampled) HIPCK(e, hipMemcpyAsync(e->bs_dev, h, L.total * 4, hipMemcpyHostToDevice, e->stream));
+            for (int j = 0; j < n; j++) {
+                const int i = order[j], slot = j % e->ctl_ring_cap;
+                if (j > 0 && slot == 0) HIPCK(e, hipStreamSynchronize(e->stream));      // (the ring of control blocks is reused)
+                int *c = e->h_ctl_ring + (size_t)slot * CTL_WORDS;
+                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos[i]; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = streams[i];
+                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
+                if ((rc = launch_step(e, pos[i]))) return rc;
+                if (i >= n_out) continue;
+                if (logits_out) HIPCK(e, hipMemcpyAsync(logits_out + (size_t)i * V, e->logits, V * 4, hipMemcpyDeviceToHost, e->stream));
+                if (!sm && next_ids) HIPCK(e, hipMemcpyAsync(next_ids + i, e->result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+                if (sm) HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n_out, i, 1, e->logits, 1u << samp_mode(sm->params[i].temperature, sm->params[i].top_p), e->stream));
+            }
+            if (sampled) HIPCK(e, hipMemcpyAsync(h + L.nrec, e->bs_dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCK(e, hipStreamSynchronize(e->stream));
+            if (attempt == 0 && take_fused_timeout(e)) continue;   // every row again, on the general plan, from the caller's windows
+            break;
+        }
+    }
+    for (int i = 0; sm && i < n_out; i++) {
+        next_ids[i] = h[L.ids + i];
+        sm->n_recent[i] = h[L.nrec + i];
+        memcpy(sm->recent + (size_t)i * sm->recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)sm->n_recent[i] * 4);
+    }
+    return NL_OK;
+}
+
+}  // namespace
+
+int nl_forward_mixed(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, int n_out, float *logits_out, int *next_ids) {
+    return forward_mixed(e, streams, tokens, pos, n, n_out, logits_out, next_ids, nullptr);
+}
+
+int nl_forward_mixed_sample(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, int n_out,
+                            const nl_sample_params *params, const float *uniforms, int *recent, int recent_stride, int *n_recent,
+                            int *next_ids) {
+    const MixedSample sm{params, uniforms, recent, recent_stride, n_recent};
+    return forward_mixed(e, streams, tokens, pos, n, n_out, nullptr, next_ids, &sm);
+}
+
+int nl_mixed_capacity(nl_handle e, int *max_rows, int *max_out) {
+    if (!e) return NL_ERR_INVALID;
+    if (e->grp) return e->fail(NL_ERR_UNSUPPORTED, "nl_mixed_capacity: device groups are not supported");
+    if (!e->finalized) return e->fail(NL_ERR_STATE, "nl_mixed_capacity before nl_finalize");
+    if (max_rows) *max_rows = mixed_max_rows(e);
+    if (max_out) *max_out = BS_MAX_ROWS;
     return NL_OK;
 }
 

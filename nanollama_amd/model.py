@@ -142,6 +142,56 @@ class LlamaModel:
             rec.ctypes.data_as(C.POINTER(C.c_int)), stride, nrec, ids))
         return [int(ids[i]) for i in range(n)], [[int(t) for t in rec[i, :nrec[i]]] for i in range(n)]
 
+    def forward_mixed(self, streams: List[int], tokens: List[int], pos: List[int], n_out: int, want_logits: bool = False):
+        """One step over rows in which a stream may appear several times (nl_forward_mixed): decode rows and chunks of the
+        prompts being admitted.  Rows [0, n_out) are output rows; returns (their greedy ids, their logits or None)."""
+        n = len(streams)
+        if len(tokens) != n or len(pos) != n:
+            raise ValueError("one token and position per row")
+        ia = lambda v: (C.c_int * max(n, 1))(*[int(x) for x in v])
+        ids = (C.c_int * max(n_out, 1))()
+        lg = np.zeros((max(n_out, 0), self.config.vocab_size), dtype=np.float32) if want_logits else None
+        _lib.check(self._h, _lib.lib().nl_forward_mixed(
+            self._h, ia(streams), ia(tokens), ia(pos), n, int(n_out),
+            lg.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, ids))
+        return [int(ids[i]) for i in range(max(n_out, 0))], lg
+
+    def forward_mixed_sample(self, streams: List[int], tokens: List[int], pos: List[int], n_out: int, params, uniforms,
+                             recents):
+        """forward_mixed followed by the sampler of forward_batch_sample on the n_out output rows (nl_forward_mixed_sample):
+        params, uniforms and recents have one entry per OUTPUT row, with forward_batch_sample's conventions.  Returns
+        (ids, recents after the step)."""
+        n, m = len(streams), int(n_out)
+        ia = lambda v: (C.c_int * max(n, 1))(*[int(x) for x in v])
+        get = lambda p, k: p[k] if isinstance(p, dict) else getattr(p, k)
+        u = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float32).reshape(-1))
+        if len(tokens) != n or len(pos) != n or m < 0 or len(params) != m or len(recents) != m or u.size != m:
+            raise ValueError("one token and position per row; one settings, uniform and window per output row")
+        ps = (_lib.NlSampleParams * max(m, 1))(*[
+            _lib.NlSampleParams(float(get(p, "temperature")), float(get(p, "top_p")), int(get(p, "top_k")),
+                                float(get(p, "rep_penalty")), int(get(p, "rep_window"))) for p in params])
+        stride = max([int(get(p, "rep_window")) for p in params] + [1])
+        rec = np.zeros((max(m, 1), stride), dtype=np.int32)
+        nrec = (C.c_int * max(m, 1))()
+        for i, r in enumerate(recents):
+            if len(r) > stride:
+                raise ValueError(f"window of row {i} holds {len(r)} ids, more than rep_window")
+            rec[i, :len(r)] = r
+            nrec[i] = len(r)
+        ids = (C.c_int * max(m, 1))()
+        ub = u if m else np.zeros(1, dtype=np.float32)
+        _lib.check(self._h, _lib.lib().nl_forward_mixed_sample(
+            self._h, ia(streams), ia(tokens), ia(pos), n, m, ps, ub.ctypes.data_as(C.POINTER(C.c_float)),
+            rec.ctypes.data_as(C.POINTER(C.c_int)), stride, nrec, ids))
+        return [int(ids[i]) for i in range(m)], [[int(t) for t in rec[i, :nrec[i]]] for i in range(m)]
+
+    @property
+    def mixed_capacity(self):
+        """(most rows, most output rows) of one forward_mixed call."""
+        rows, out = C.c_int(0), C.c_int(0)
+        _lib.check(self._h, _lib.lib().nl_mixed_capacity(self._h, C.byref(rows), C.byref(out)))
+        return rows.value, out.value
+
     def set_gamma(self, indices, values) -> None:
         """model.Gamma = gamma (go/main.go:79): indices int32 [n], values [n, dim] float32 or float16."""
         idx = np.ascontiguousarray(indices, dtype=np.int32)

@@ -3,6 +3,7 @@
     GET  /        chat UI (a minimal page of our own; the reference embeds go/ui.html)
     POST /chat    {"messages":[{"role","content"}], "temperature", "max_tokens", "top_k"} -> {"response"}
     GET  /health  {"status","params_millions","layers","dim","heads","kv_heads","vocab_size","gamma_loaded"}
+                  (+ "steps","prefill_chunk","max_step_gap_ms" with --parallel N)
 
 One generation at a time (the model handle is single-caller): a lock around GenerateQuiet, as go/serve.go:56,106-108.
 With --parallel N the engine is a BatchScheduler (batch_serve.py): concurrent requests decode as one batch, no lock.
@@ -65,9 +66,12 @@ def handle_health(engine):
     """GET /health (go/serve.go:114-126)."""
     from .cli import estimate_params
     c = engine.model.config
-    return {"status": "ok", "params_millions": estimate_params(c) // 1_000_000, "layers": c.num_layers,
-            "dim": c.embed_dim, "heads": c.num_heads, "kv_heads": c.num_kv_heads, "vocab_size": c.vocab_size,
-            "gamma_loaded": engine.model.gamma is not None}
+    out = {"status": "ok", "params_millions": estimate_params(c) // 1_000_000, "layers": c.num_layers,
+           "dim": c.embed_dim, "heads": c.num_heads, "kv_heads": c.num_kv_heads, "vocab_size": c.vocab_size,
+           "gamma_loaded": engine.model.gamma is not None}
+    if isinstance(engine, BatchScheduler):       # --parallel N: the scheduler's counters (tools/bench_serve_parallel.py)
+        out.update(steps=engine.steps, prefill_chunk=engine.prefill_chunk, max_step_gap_ms=round(engine.max_step_gap_ms, 3))
+    return out
 
 
 def make_handler(engine, defaults: GenParams):

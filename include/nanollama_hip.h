@@ -158,6 +158,15 @@ NL_API int nl_sample_decode(nl_handle h, int stream, int pos, int n_steps, const
  * and an fp16 hi+lo activation split differ), greedy continuations are identical; other formats run
  * the single-token plan n times (bitwise equal).  pos0 + n must be <= seq_len. */
 NL_API int nl_prefill(nl_handle h, int stream, const int *tokens, int n, int pos0, float *last_logits_out);
+/* nl_prefill that also scores: feeds tokens[0..n) at pos0.. of `stream` exactly as nl_prefill does, and for every row i
+ * returns log P(targets[i] | tokens[0..i] and the stream's earlier positions) -- natural log, of the softmax over the row's
+ * logits -- in logprob_out[i] (targets[i] == -1: row not scored, 0.0f) and the row's greedy id in argmax_out[i] (may be NULL).
+ * targets is separate from tokens so a text longer than seq_len can be scored in windows and so a caller can score a
+ * continuation only.  K/V rows, position marks and the last row's logits / argmax are left exactly as nl_prefill leaves them
+ * (nl_sample_decode / nl_forward may follow).  No logits leave the device.  Device groups: NL_ERR_UNSUPPORTED.
+ * No reference counterpart (the Go host only generates); the quantity is nanollama/core_eval.py's cross entropy per token. */
+NL_API int nl_score(nl_handle h, int stream, const int *tokens, const int *targets, int n, int pos0,
+                    float *logprob_out, int *argmax_out);
 /* One Forward for each of n (stream, token, pos) triples -- the concurrent decode streams of a
  * serving host.  logits_out (may be NULL) is n x vocab; next_ids (may be NULL) receives each
  * stream's greedy argmax.  Streams must be distinct. */
@@ -264,6 +273,11 @@ NL_API int nl_op_sample(int device, float *logits, int vocab, const nl_sample_pa
  * poisoned first, so a row reading a scratch word it did not write in this call does not go unseen. */
 NL_API int nl_op_sample_rows(int device, float *logits, int vocab, int n, const nl_sample_params *params,
                              const float *uniforms, int *recent, int recent_stride, int *n_recent, int *picked);
+
+/* The row reduction alone on host logits [n][vocab] (parity tests of the kernel): the launches are nl_score's.  lse_out and
+ * argmax_out may be NULL; any vocab >= 1. */
+NL_API int nl_op_score_rows(int device, const float *logits, int vocab, int n, const int *targets,
+                            float *logprob_out, float *lse_out, int *argmax_out);
 
 /* == tensor-parallel communicator (RCCL over xGMI) ========================= */
 #define NL_COMM_ID_BYTES 128

@@ -92,7 +92,7 @@ EXPORTS = ["nl_build_info", "nl_set_gamma", "nl_abi_version", "nl_device_count",
            "nl_comm_init", "nl_group_forward", "nl_debug_stamps", "nl_sample_decode", "nl_op_sample", "nl_p2p_export",
            "nl_p2p_import", "nl_p2p_info", "nl_p2p_loopback", "nl_op_exp", "nl_plan_info", "nl_persist_info", "nl_create_group", "nl_host_logits",
            "nl_op_gran16_soak", "nl_forward_batch_sample", "nl_op_sample_rows", "nl_forward_mixed", "nl_forward_mixed_sample",
-           "nl_mixed_capacity"]
+           "nl_mixed_capacity", "nl_score", "nl_op_score_rows"]
 
 
 def lib():
@@ -153,6 +153,8 @@ def lib():
     L.nl_forward_mixed.argtypes = [vp, ip, ip, ip, i32, i32, fp, ip]
     L.nl_forward_mixed_sample.argtypes = [vp, ip, ip, ip, i32, i32, C.POINTER(NlSampleParams), fp, ip, i32, ip, ip]
     L.nl_mixed_capacity.argtypes = [vp, ip, ip]
+    L.nl_score.argtypes = [vp, i32, ip, ip, i32, i32, fp, ip]
+    L.nl_op_score_rows.argtypes = [i32, fp, i32, i32, ip, fp, fp, ip]
     _lib = L
     return L
 

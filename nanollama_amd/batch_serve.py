@@ -11,7 +11,10 @@ thread owns the model handle (single-caller) and runs a loop of steps; every ste
      not emitted (go/main.go:203); otherwise the id is emitted, and the output cap, max_tokens and the end of the context
      each end the request.
 
-A finished request gets its text and frees its stream; a request that arrives meanwhile joins at the next step.  Settings
+A finished request gets its text and frees its stream; a request that arrives meanwhile joins at the next step.
+POST /score jobs (score(ids, n_context)) wait in the same queue: the worker gives one a free stream, scores on it
+(score.score_ids: reset and nl_score per window) and frees the stream again -- it occupies the worker as a whole-prompt
+prefill at admission does.
 With prefill_chunk = N > 0 (--prefill-chunk) admission no longer runs the prompt: it only resets the stream and seeds the
 request's generator, and every step is ONE forward_mixed_sample call (nl_forward_mixed_sample) -- the decoding requests as
 output rows, then up to N prompt tokens of the admitted requests in admission order.  A prompt may span several steps and
@@ -35,6 +38,7 @@ import numpy as np
 
 from .engine import GenParams
 from .engine_text import TextOutput
+from .score import ScoreResult, score_ids
 
 MAX_PARALLEL = 64            # rows of one nl_forward_batch_sample call (the LM head's batch)
 MAX_VOCAB = 131072           # the device sampler's vocabularies
@@ -55,6 +59,15 @@ class _Request:
     params: GenParams
     done: threading.Event = field(default_factory=threading.Event)
     text: str = ""
+    error: Optional[RequestError] = None
+
+
+@dataclass
+class _ScoreJob:
+    ids: List[int]
+    n_context: int
+    done: threading.Event = field(default_factory=threading.Event)
+    result: Optional[ScoreResult] = None
     error: Optional[RequestError] = None
 
 
@@ -123,6 +136,19 @@ class BatchScheduler:
             raise req.error
         return req.text
 
+    def score(self, ids: List[int], n_context: int = 1) -> ScoreResult:
+        """score.score_ids(model, ids, a free stream, n_context) on the worker; blocks until done.  Raises RequestError (500)."""
+        job = _ScoreJob([int(t) for t in ids], int(n_context))
+        with self._cv:
+            if self._closed:
+                raise RequestError(500, "scheduler closed")
+            self._queue.append(job)
+            self._cv.notify()
+        job.done.wait()
+        if job.error is not None:
+            raise job.error
+        return job.result
+
     def close(self) -> None:
         with self._cv:
             self._closed = True
@@ -135,11 +161,25 @@ class BatchScheduler:
         free.append(row.stream)
         row.req.done.set()
 
-    def _fail(self, req: _Request, status: int, exc: BaseException) -> None:
+    def _fail(self, req, status: int, exc: BaseException) -> None:
         req.error = RequestError(status, f"{type(exc).__name__}: {exc}")
         req.done.set()
 
+    def _score(self, job: _ScoreJob, stream: int, free: List[int]) -> None:
+        try:
+            self.model.reset(stream)
+            job.result = score_ids(self.model, job.ids, stream, job.n_context)
+        except Exception as exc:                        # engine error: this job fails, the scheduler goes on
+            free.append(stream)
+            self._fail(job, 500, exc)
+            return
+        free.append(stream)
+        job.done.set()
+
     def _admit(self, req: _Request, stream: int, active: List[_Row], free: List[int]) -> None:
+        if isinstance(req, _ScoreJob):
+            self._score(req, stream, free)
+            return
         cfg = self.model.config
         p = req.params
         rng = np.random.default_rng(int(self.rng.integers(0, 2 ** 63 - 1)))

@@ -2,7 +2,8 @@
 
     python -m nanollama_amd --model m.gguf --prompt "Hello"            (one shot)
     python -m nanollama_amd --model m.gguf --interactive               (REPL, /quit /exit /info)
-    python -m nanollama_amd --model m.gguf --serve --port 8080         (HTTP: GET /, POST /chat, GET /health)
+    python -m nanollama_amd --model m.gguf --serve --port 8080         (HTTP: GET /, POST /chat, POST /score, GET /health)
+    python -m nanollama_amd --model m.gguf --score text.txt            (log-probability, perplexity, bits per byte of a text)
     python -m nanollama_amd --model m.gguf --serve --parallel 16 --prefill-chunk 64   (batched server, chunked admission)
 """
 from __future__ import annotations
@@ -45,7 +46,32 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --serve --parallel N: admit prompts in chunks of up to this many tokens that share a step with "
                          "the decoding requests (mixed steps) instead of running each prompt whole while the others wait; "
                          "0 = whole prompts at admission")
+    ap.add_argument("--score", default="", metavar="PATH",
+                    help="score the text in PATH ('-': stdin) instead of generating: prints tokens, nll, ppl, bits per byte "
+                         "and tokens/s; not with --serve, --interactive or --prompt")
     return ap
+
+
+def check_score(args) -> None:
+    """--score: a mode of its own, on one GPU (a device group has no scoring entry point)."""
+    if not args.score:
+        return
+    for flag, on in (("--serve", args.serve), ("--interactive", args.interactive), ("--prompt", bool(args.prompt))):
+        if on:
+            raise RuntimeError(f"--score cannot be combined with {flag}")
+    if args.gpus > 1:
+        raise RuntimeError("--score needs --gpus 1 (scoring is not available on a device group)")
+
+
+def run_score(eng, path: str, out=None) -> None:
+    import time
+    from .score import score_text
+    out = out or sys.stdout
+    text = sys.stdin.read() if path == "-" else open(path, encoding="utf-8").read()
+    t0 = time.perf_counter()
+    r = score_text(eng.model, eng.tokenizer, text)
+    dt = time.perf_counter() - t0
+    print(f"tokens {r.n_tokens}  nll {r.nll:.6f}  ppl {r.ppl:.4f}  bpb {r.bpb:.6f}  {r.n_tokens / dt if dt > 0 else 0.0:.1f} tokens/s", file=out)
 
 
 MAX_MIXED_ROWS = 512         # rows of one mixed step (nl_mixed_capacity reports the handle's own limit, at most this)
@@ -159,6 +185,7 @@ def main(argv=None) -> int:
             return 0
         check_parallel(args)
         check_prefill_chunk(args)
+        check_score(args)
         eng = load_engine(args)
         if args.prefill_chunk > 0:
             check_prefill_chunk(args, eng.model.mixed_capacity[0])
@@ -166,6 +193,13 @@ def main(argv=None) -> int:
         print(f"error: {exc}", file=sys.stderr)
         return 1
     params = GenParams(max_tokens=args.max_tokens, temperature=args.temp, top_p=args.top_p, top_k=args.top_k)
+    if args.score:
+        try:
+            run_score(eng, args.score)
+        except (OSError, UnicodeDecodeError, RuntimeError) as exc:
+            print(f"error: {exc}", file=sys.stderr)
+            return 1
+        return 0
     if args.serve:
         from .serve import run_server
         if batched(args):

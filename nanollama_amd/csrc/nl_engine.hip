@@ -15,6 +15,7 @@
 #include "nl_dgemm.h"
 #include "nl_batch.h"
 #include "nl_sample.h"
+#include "nl_score.h"
 #include "nl_p2p.h"
 #include "nl_block.h"
 #include "nl_group.h"
@@ -107,6 +108,8 @@ namespace {
 //   NL_DGEMM_MAX_TOKENS           by shape    step     longest step dgemm_kernel takes (dgemm_step_ok)
 //   NL_DGEMM_HEAD                 1           step     0: a decode batch's LM head stays bnorm + split-K + argmax
 //   NL_MIXED_ATTN                 1           step     0: every row of a mixed step (nl_forward_mixed) attends on the per-token kernel
+//   NL_SCORE_SLAB                 512         step     rows of nl_score's LM head per launch; its logits scratch is this many rows (64 /
+//                                                      128 / 256 / 512 measured, EXPERIMENTS "Scoring on the device"; clamped to 1 .. 2048)
 //   NL_MIXED_ATTN_MIN             512         step     (row, visible 128-key chunk) pairs of a mixed step's prompt segments from which
 //                                                      they take the segment-tile kernel (0: always; below it the second launch costs
 //                                                      more than the K / V fetches it saves)
@@ -157,7 +160,7 @@ struct StepKnobs {
     int qg2_min_tokens = knob_int("NL_QG2_MIN_TOKENS", 128), kv16_min_tokens = knob_int("NL_KV16_MIN_TOKENS", 256), att_run = knob_int("NL_ATT_RUN", 0);
     bool fold_norm = !knob_off("NL_FOLD_NORM"), rope_in_attn = !knob_off("NL_ROPE_IN_ATTN"), dgemm = !knob_off("NL_DGEMM"),
          dgemm_head = !knob_off("NL_DGEMM_HEAD"), mixed_attn = !knob_off("NL_MIXED_ATTN");
-    int mixed_attn_min = knob_int("NL_MIXED_ATTN_MIN", 512);
+    int mixed_attn_min = knob_int("NL_MIXED_ATTN_MIN", 512), score_slab = std::max(1, std::min(2048, knob_int("NL_SCORE_SLAB", 512)));
     std::optional<int> dgemm_max_tokens = knob_opt("NL_DGEMM_MAX_TOKENS");
     bool operator==(const StepKnobs &) const = default;
     int x1_gemm() const { return prefill == Precision::fp16x1 || prefill == Precision::fp16x1_gemm; }
@@ -306,6 +309,8 @@ struct nl_engine {
     unsigned long long *h_done = nullptr, *d_done = nullptr;
     unsigned box_seq = 0;
     float *d_h_logits = nullptr; // device address of h_logits (the LM head of a per-call Forward stores the logits there itself)
+    int *sc_targets = nullptr, *sc_argmax = nullptr;   // nl_score on single-token steps: [seq_len] targets and results, one per step
+    float *sc_logprob = nullptr;
     float *h_logits = nullptr;   // pinned [vocab] + one int behind it: the per-call read-backs of nl_forward / nl_forward_argmax /
                                  // nl_prefill land here by DMA and are copied to the caller's (pageable) buffer by the CPU -- a
                                  // hipMemcpyAsync to pageable memory is a staged, blocking copy inside the runtime (128 KB: ~90 us)
@@ -339,6 +344,13 @@ struct nl_engine {
         long long *tkv = nullptr;                    // [cap]: stream * kv_stream_stride + pos * hd
         int *h_meta = nullptr;  // pinned [5][cap]: token | position | stream | attention workgroup list | partials per token
         uint4 *kv16 = nullptr;  // one layer's K / V^T of a prompt's stream as fp16 hi / lo LDS images (nl_batch.h Kv16Image)
+        // nl_score (allocated at its first multi-token call, score_alloc): the logits of one slab of rows, and per row of a
+        // step its target id and the results of score_rows_kernel (nl_score.h)
+        int sc_slab = 0;                 // rows sc_logits holds
+        float *sc_logits = nullptr;      // [sc_slab][vocab]
+        int *sc_targets = nullptr, *sc_argmax = nullptr;      // [cap]
+        float *sc_logprob = nullptr;     // [cap]
+        int *h_targets = nullptr;        // pinned [cap]
     } bt;
 
     // Concurrent sub-batches of a decode batch (nl_forward_batch): the streams of a batch are independent (go/serve.go:106-108
@@ -2070,7 +2082,8 @@ hipError_t launch_qgemm_plain(nl_engine *e, nl_engine::Batch &bt, const PackedMa
 }
 
 // One multi-token step: n <= 64 (token, pos, stream) triples through every layer on the MFMA path.
-// lm_mode: 0 = no LM head, 1 = logits + argmax for every token, 2 = logits + argmax for the LAST token only.
+// lm_mode: 0 = no LM head, 1 = logits + argmax for every token, 2 = logits + argmax for the LAST token only; 4 / 3 = 0 / 2 after
+// every row has been scored against bt.sc_targets (nl_score; the caller has run score_alloc and uploaded the targets).
 // The caller has filled bt.h_meta; stream-ordered, no synchronisation inside.
 // mx (nl_forward_mixed): a stream may own several rows.  The LM head of lm_mode 1 covers rows [0, n_out) only; rows [0, n_tok)
 // attend on the per-token kernel, the rest through the n_work entries of the segment work list the caller left in h_meta
@@ -2338,6 +2351,22 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
         } else {
             LCK(qg(e, b, L.down, n, b.x, D, b.x, st, k, &pend, b.kpart, nullptr, down_in));
         }
+    }
+    if (lm_mode >= 3) {
+        // nl_score: every row's logits, a slab of rows at a time, reduced on the spot to (log-probability of the row's target,
+        // greedy id) by score_rows_kernel -- three launches per slab (+ the split-K sum where the head's GEMM splits), the
+        // slab's logits never leave the device.  A pending split-K output of the last down projection is folded into x first
+        // (its slabs live in kpart, the scratch of the head's own split-K); the sums are those the per-slab norm would make.
+        if (pend.ks > 1) LCK(norm(e->output_norm, e->lm_head, 0, n));
+        const int slab = std::min(k.score_slab, b.sc_slab);
+        for (int first = 0; first < n; first += slab) {
+            const int cnt = std::min(slab, n - first);
+            LCK(norm(e->output_norm, e->lm_head, first, cnt));
+            LCK(launch_qgemm_plain(e, b, e->lm_head, cnt, b.sc_logits, c.vocab, k, st));
+            const ScoreRowsParams SP{b.sc_logits, c.vocab, c.vocab, b.sc_targets + first, b.sc_logprob + first, nullptr, b.sc_argmax + first};
+            LCK(launch_score_rows(SP, cnt, st));
+        }
+        lm_mode = lm_mode == 3 ? 2 : 0;     // ... and the last row once more as nl_prefill runs it: what the call leaves behind is nl_prefill's, bit for bit
     }
     if (lm_mode) {
         // logits rows [0, cnt) of bt.logits / ids [0, cnt): all tokens (mode 1, n <= lm_cap) or just the last (mode 2)
@@ -3269,11 +3298,13 @@ int nl_destroy(nl_handle e) {
     if (e->gamma_val) hipFree(e->gamma_val);
     for (void *c : e->arena_chunks) hipFree(c);
     if (e->stage) hipFree(e->stage);
+    for (void *p : {(void *)e->sc_targets, (void *)e->sc_argmax, (void *)e->sc_logprob}) if (p) hipFree(p);
     auto batch_free = [](nl_engine::Batch &b) {
         void *bb[] = {b.x, b.qkv, b.q, b.g, b.u, b.logits, b.part_o, b.part_ml, b.tok /* | pos | stream */, b.ids, b.kpart, b.kpart2,
-                      b.xfrag, b.xfrag2, b.ssq, b.nscale, b.kv16, b.tcos, b.tsin, b.tkv};
+                      b.xfrag, b.xfrag2, b.ssq, b.nscale, b.kv16, b.tcos, b.tsin, b.tkv, b.sc_logits, b.sc_targets, b.sc_argmax, b.sc_logprob};
         for (void *p : bb) if (p) hipFree(p);
         if (b.h_meta) hipHostFree(b.h_meta);
+        if (b.h_targets) hipHostFree(b.h_targets);
     };
     destroy_step_graphs(e);
     batch_free(e->bt);
@@ -3764,6 +3795,136 @@ int nl_prefill(nl_handle e, int stream, const int *tokens, int n, int pos0, floa
     if (int prc = p2p_check(e)) return prc;
     if (last_logits_out && last_logits_out != e->h_logits) memcpy(last_logits_out, e->h_logits, (size_t)e->cfg.vocab * 4);
     return NL_OK;
+}
+
+namespace {
+// nl_score's scratch of the multi-token path: the per-row arrays once per handle, the logits of a slab of rows grow-only (the
+// caller holds g_setup_mu; b is allocated)
+int score_alloc(nl_engine *e, nl_engine::Batch &b, const StepKnobs &k) {
+    if (!b.sc_logprob) {
+        HIPCK(e, dalloc(&b.sc_targets, (size_t)b.cap, &e->bytes_state));
+        HIPCK(e, dalloc(&b.sc_argmax, (size_t)b.cap, &e->bytes_state));
+        HIPCK(e, dalloc(&b.sc_logprob, (size_t)b.cap, &e->bytes_state));
+        HIPCK(e, hipHostMalloc((void **)&b.h_targets, (size_t)b.cap * sizeof(int), hipHostMallocDefault));
+    }
+    const int slab = std::min(k.score_slab, b.cap);
+    if (b.sc_slab < slab) {
+        if (b.sc_logits) {
+            HIPCK(e, hipStreamSynchronize(e->stream));
+            HIPCK(e, hipFree(b.sc_logits));
+            e->bytes_state -= (size_t)b.sc_slab * e->cfg.vocab * sizeof(float);
+            b.sc_logits = nullptr; b.sc_slab = 0;
+        }
+        HIPCK(e, dalloc(&b.sc_logits, (size_t)slab * e->cfg.vocab, &e->bytes_state));
+        b.sc_slab = slab;
+    }
+    return NL_OK;
+}
+}  // namespace
+
+int nl_score(nl_handle e, int stream, const int *tokens, const int *targets, int n, int pos0, float *logprob_out, int *argmax_out) {
+    if (!e) return NL_ERR_INVALID;
+    if (e->grp || e->G != 1) return e->fail(NL_ERR_UNSUPPORTED, "nl_score: device groups are not supported");
+    if (!tokens || !targets || !logprob_out || n < 0) return NL_ERR_INVALID;
+    if (n == 0) return NL_OK;
+    int rc = check_step_args(e, stream, tokens[0], pos0);
+    if (rc) return rc;
+    if (pos0 + n > e->cfg.seq_len) return e->fail(NL_ERR_INVALID, "score of %d tokens at pos %d exceeds seq_len %d", n, pos0, e->cfg.seq_len);
+    for (int i = 0; i < n; i++) {
+        if (tokens[i] < 0 || tokens[i] >= e->cfg.vocab) return e->fail(NL_ERR_INVALID, "token %d out of range [0,%d)", tokens[i], e->cfg.vocab);
+        if (targets[i] < -1 || targets[i] >= e->cfg.vocab) return e->fail(NL_ERR_INVALID, "target %d out of range [-1,%d)", targets[i], e->cfg.vocab);
+    }
+    HIPCK(e, hipSetDevice(e->dev));
+    if (int qrc = pd_session_close(e)) return qrc;
+    if ((rc = note_positions(e, stream, pos0, n))) return rc;
+    const StepKnobs k;
+    if (n >= process_knobs().batch_min && batch_supported(e)) {
+        // nl_prefill's tiles, each with the scoring LM head (batched_step, lm_mode 3)
+        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k)) || (rc = score_alloc(e, e->bt, k))) return rc; }
+        nl_engine::Batch &b = e->bt;
+        for (int t0 = 0; t0 < n; t0 += b.cap) {
+            const int m = std::min(b.cap, n - t0);
+            HIPCK(e, hipStreamSynchronize(e->stream));  // h_meta and h_targets are reused per tile
+            for (int i = 0; i < m; i++) {
+                b.h_meta[i] = tokens[t0 + i];
+                b.h_meta[b.cap + i] = pos0 + t0 + i;
+                b.h_meta[2 * b.cap + i] = stream;
+                b.h_targets[i] = targets[t0 + i];
+            }
+            HIPCK(e, hipMemcpyAsync(b.sc_targets, b.h_targets, (size_t)m * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            const bool last = t0 + m == n;
+            if ((rc = batched_step(e, b, e->stream, m, last ? 3 : 4, k, true))) return rc;
+            if (last) {
+                HIPCK(e, hipMemcpyAsync(e->logits, b.logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
+                HIPCK(e, hipMemcpyAsync(e->result, b.ids, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+            }
+            // (a text of at most b.cap tokens -- 2048, or seq_len when that is shorter -- is one tile: one read-back of its results)
+            HIPCK(e, hipMemcpyAsync(logprob_out + t0, b.sc_logprob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+            if (argmax_out) HIPCK(e, hipMemcpyAsync(argmax_out + t0, b.sc_argmax, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        }
+    } else {
+        // the single-token plan per token, each step's logits reduced where the step left them
+        if (!e->sc_logprob) {
+            std::lock_guard<std::mutex> setup(g_setup_mu);
+            HIPCK(e, dalloc(&e->sc_targets, (size_t)e->cfg.seq_len, &e->bytes_state));
+            HIPCK(e, dalloc(&e->sc_argmax, (size_t)e->cfg.seq_len, &e->bytes_state));
+            HIPCK(e, dalloc(&e->sc_logprob, (size_t)e->cfg.seq_len, &e->bytes_state));
+        }
+        HIPCK(e, hipMemcpyAsync(e->sc_targets, targets, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        for (int attempt = 0;; attempt++) {
+            for (int i = 0; i < n; i++) {
+                int *c = e->h_ctl_ring + (size_t)i * CTL_WORDS;
+                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos0 + i; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = stream;
+                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
+                if ((rc = launch_step(e, pos0 + i))) return rc;
+                const ScoreRowsParams SP{e->logits, e->cfg.vocab, e->cfg.vocab, e->sc_targets + i, e->sc_logprob + i, nullptr, e->sc_argmax + i};
+                HIPCK(e, launch_score_rows(SP, 1, e->stream));
+            }
+            HIPCK(e, hipStreamSynchronize(e->stream));
+            if (attempt == 0 && take_fused_timeout(e)) continue;   // the prompt again, on the general plan: every result is rewritten
+            break;
+        }
+        HIPCK(e, hipMemcpyAsync(logprob_out, e->sc_logprob, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        if (argmax_out) HIPCK(e, hipMemcpyAsync(argmax_out, e->sc_argmax, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCK(e, hipStreamSynchronize(e->stream));
+    if (int prc = p2p_check(e)) return prc;
+    return NL_OK;
+}
+
+int nl_op_score_rows(int device, const float *logits, int vocab, int n, const int *targets, float *logprob_out, float *lse_out,
+                     int *argmax_out) {
+    if (!logits || !targets || !logprob_out || vocab <= 0 || n < 0) return NL_ERR_INVALID;
+    for (int i = 0; i < n; i++)
+        if (targets[i] < -1 || targets[i] >= vocab) return NL_ERR_INVALID;
+    if (n == 0) return NL_OK;
+    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
+    float *d_logits = nullptr, *d_lp = nullptr, *d_lse = nullptr;
+    int *d_t = nullptr, *d_am = nullptr;
+    int rc = NL_ERR_HIP;
+    do {
+        if (hipMalloc((void **)&d_logits, (size_t)n * vocab * 4) != hipSuccess) break;
+        if (hipMalloc((void **)&d_lp, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_lse, (size_t)n * 4) != hipSuccess) break;
+        if (hipMalloc((void **)&d_t, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_am, (size_t)n * 4) != hipSuccess) break;
+        if (hipMemcpy(d_logits, logits, (size_t)n * vocab * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_t, targets, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        // (poison: a row the kernel does not write does not go unseen)
+        if (hipMemset(d_lp, 0xff, (size_t)n * 4) != hipSuccess || hipMemset(d_lse, 0xff, (size_t)n * 4) != hipSuccess ||
+            hipMemset(d_am, 0xff, (size_t)n * 4) != hipSuccess) break;
+        const int slab = StepKnobs().score_slab;     // nl_score's launches: a slab of rows each, at the row pitch of its scratch
+        bool ok = true;
+        for (int first = 0; first < n && ok; first += slab) {
+            const ScoreRowsParams SP{d_logits + (size_t)first * vocab, vocab, vocab, d_t + first, d_lp + first, d_lse + first, d_am + first};
+            ok = launch_score_rows(SP, std::min(slab, n - first), (hipStream_t)0) == hipSuccess;
+        }
+        if (!ok || hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(logprob_out, d_lp, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (lse_out && hipMemcpy(lse_out, d_lse, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (argmax_out && hipMemcpy(argmax_out, d_am, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = NL_OK;
+    } while (0);
+    for (void *p : {(void *)d_logits, (void *)d_lp, (void *)d_lse, (void *)d_t, (void *)d_am}) if (p) (void)hipFree(p);
+    return rc;
 }
 
 int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, float *logits_out,

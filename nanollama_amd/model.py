@@ -104,6 +104,21 @@ class LlamaModel:
         out = self.state.logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None
         _lib.check(self._h, _lib.lib().nl_prefill(self._h, stream, arr, len(tokens), int(pos0), out))
 
+    def score(self, tokens: List[int], targets: List[int], pos0: int = 0, stream: int = 0):
+        """prefill that also scores (nl_score): row i's natural-log probability of targets[i] given tokens[..i] and the
+        stream's earlier positions (targets[i] == -1: not scored, 0.0) and its greedy id.  No logits leave the device; the
+        stream is left as prefill leaves it.  Returns (logprobs float32[n], argmax int32[n])."""
+        tok = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        if tok.size != tgt.size:
+            raise ValueError("one target per token")
+        lp = np.zeros(tok.size, dtype=np.float32)
+        am = np.zeros(tok.size, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        _lib.check(self._h, _lib.lib().nl_score(self._h, stream, tok.ctypes.data_as(ip), tgt.ctypes.data_as(ip), int(tok.size),
+                                                int(pos0), lp.ctypes.data_as(C.POINTER(C.c_float)), am.ctypes.data_as(ip)))
+        return lp, am
+
     def forward_batch(self, streams: List[int], tokens: List[int], pos: List[int], want_logits: bool = False):
         n = len(streams)
         ia = lambda v: (C.c_int * n)(*[int(x) for x in v])
@@ -459,6 +474,25 @@ def op_sample_rows(logits: np.ndarray, params, uniforms, recents, device: int = 
     if rc != 0:
         raise _lib.NlError(rc, "nl_op_sample_rows")
     return [int(picked[i]) for i in range(n)], lg, [[int(t) for t in rec[i, :nrec[i]]] for i in range(n)]
+
+
+def op_score_rows(logits: np.ndarray, targets, device: int = 0):
+    """The row reduction of nl_score (nl_op_score_rows) on host logits [n, vocab]: per row log P(target) (target -1: 0.0),
+    the log-sum-exp and the greedy id.  Returns (logprob float32[n], lse float32[n], argmax int32[n])."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim != 2:
+        raise ValueError("logits must be [rows, vocab]")
+    n, vocab = lg.shape
+    tgt = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    if tgt.size != n:
+        raise ValueError("one target per logits row")
+    lp, lse, am = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+    rc = _lib.lib().nl_op_score_rows(device, lg.ctypes.data_as(fp), int(vocab), int(n), tgt.ctypes.data_as(ip),
+                                     lp.ctypes.data_as(fp), lse.ctypes.data_as(fp), am.ctypes.data_as(ip))
+    if rc != 0:
+        raise _lib.NlError(rc, "nl_op_score_rows")
+    return lp, lse, am
 
 
 def op_exp(x: np.ndarray, device: int = 0) -> np.ndarray:

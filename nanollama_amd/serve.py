@@ -2,6 +2,8 @@
 
     GET  /        chat UI (a minimal page of our own; the reference embeds go/ui.html)
     POST /chat    {"messages":[{"role","content"}], "temperature", "max_tokens", "top_k"} -> {"response"}
+    POST /score   {"text"} or {"prompt","continuation"} (+ "details": true) -> {"tokens","logprob","nll","ppl","bpb"}
+                  (+ "token_logprobs"); no counterpart in go/serve.go -- the quantity is nanollama/core_eval.py's bits per byte
     GET  /health  {"status","params_millions","layers","dim","heads","kv_heads","vocab_size","gamma_loaded"}
                   (+ "steps","prefill_chunk","max_step_gap_ms" with --parallel N)
 
@@ -12,12 +14,14 @@ from __future__ import annotations
 
 import contextlib
 import json
+import math
 import threading
 from dataclasses import replace
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 
 from .batch_serve import BatchScheduler, RequestError
 from .engine import GenParams
+from .score import score_continuation, score_text
 
 UI_HTML = b"""<!doctype html><html><head><meta charset="utf-8"><title>nanollama</title>
 <style>body{font-family:sans-serif;max-width:46em;margin:2em auto}#log{white-space:pre-wrap;border:1px solid #ccc;
@@ -60,6 +64,46 @@ def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
     except RequestError as exc:             # (batch scheduler: settings it cannot serve, or an engine error)
         return exc.status, str(exc)
     return 200, {"response": result}
+
+
+def handle_score(engine, lock, body: bytes):
+    """POST /score.  {"text"}: the whole text behind BOS, bpb over its bytes; {"prompt", "continuation"}: the continuation given
+    the prompt, bpb over the continuation's bytes.  Returns (status, payload)."""
+    try:
+        req = json.loads(body.decode("utf-8") or "{}")
+        if not isinstance(req, dict):
+            raise ValueError("request must be a JSON object")
+        text, prompt, cont = req.get("text"), req.get("prompt"), req.get("continuation")
+        if text is not None and (prompt is not None or cont is not None):
+            raise ValueError('either "text" or "prompt" and "continuation"')
+        if text is None and (prompt is None or cont is None):
+            raise ValueError('"text", or "prompt" and "continuation", required')
+        if not all(isinstance(v, str) for v in (text, prompt, cont) if v is not None):
+            raise ValueError("text fields must be strings")
+        if (text if text is not None else cont) == "":
+            raise ValueError("nothing to score: empty " + ("text" if text is not None else "continuation"))
+    except (ValueError, UnicodeDecodeError) as exc:
+        return 400, "bad request: " + str(exc)
+    # a BatchScheduler scores on a stream of its own worker (its score(ids, n_context)); a TextEngine's handle is single-caller
+    if isinstance(engine, BatchScheduler):
+        run = lambda model, ids, stream, n_context: engine.score(ids, n_context)
+    else:
+        from .score import score_ids as run
+    try:
+        with lock:
+            if text is not None:
+                r = score_text(engine.model, engine.tokenizer, text, score=run)
+            else:
+                r = score_continuation(engine.model, engine.tokenizer, prompt, cont, score=run)
+    except RequestError as exc:
+        return exc.status, str(exc)
+    if r.n_tokens == 0:
+        return 400, "bad request: nothing to score (the continuation adds no token to the prompt)"
+    num = lambda v: v if math.isfinite(v) else None          # (a target whose logit is -inf: JSON has no infinity)
+    out = {"tokens": r.n_tokens, "logprob": num(r.logprob), "nll": num(r.nll), "ppl": num(r.ppl), "bpb": num(r.bpb)}
+    if req.get("details") is True:
+        out["token_logprobs"] = [num(v) for v in r.token_logprobs]
+    return 200, out
 
 
 def handle_health(engine):
@@ -107,17 +151,20 @@ def make_handler(engine, defaults: GenParams):
                 self.wfile.write(UI_HTML)
             elif self.path == "/health":
                 self._json(200, handle_health(engine))
-            elif self.path == "/chat":
+            elif self.path in ("/chat", "/score"):
                 self._text(405, "POST only")
             else:
                 self._text(404, "404 page not found")
 
         def do_POST(self):
-            if self.path != "/chat":
+            if self.path not in ("/chat", "/score"):
                 self._text(404, "404 page not found")
                 return
             n = int(self.headers.get("Content-Length") or 0)
-            status, payload = handle_chat(engine, defaults, lock, self.rfile.read(n))
+            if self.path == "/score":
+                status, payload = handle_score(engine, lock, self.rfile.read(n))
+            else:
+                status, payload = handle_chat(engine, defaults, lock, self.rfile.read(n))
             if isinstance(payload, str):
                 self._text(status, payload)
             else:

@@ -79,6 +79,38 @@ def test_gemv_edge_values(hip, orc):
         assert np.all(np.abs(got - want) <= 2e-5 * (1 + np.abs(want)))
         zero = hip.op_matmul(raw, t, np.zeros(cols, np.float32), rows, cols)
         assert np.all(zero == 0)
+    # Q5_0, Q4_K (d and dmin) and Q6_K: random quant bytes, the same fp16 bit patterns -- finite scales only (the
+    # reference scales Q5_0 / Q6_K element by element, the device block sums: inf * 0 differs by construction).
+    # A row here sums up to 768 terms of both signs and of magnitudes from 6e-8 to 1e5, and the bound is relative to the
+    # RESULT: on a row that cancels to a few per cent of its terms, two correct float32 summation orders differ by more
+    # (the float32 reference itself misses the float64 product by more than the bound there).  So the draw is repeated
+    # until the reference -- alone, no device value enters -- is within a quarter of the bound of the float64 product
+    # (decoded by tests/exact_mats.py) on every row; the device is then held to the whole bound against the reference.
+    import exact_mats as em
+    rows, cols = 48, 768                     # three super blocks per row: the pattern pairing shifts from row to row
+    for kind, fields in (("q5_0", (0,)), ("q4_k", (0, 2)), ("q6_k", (208,))):
+        t, (per, bsz) = em.GGML_TYPE[kind], em.BLOCK[kind]
+        for draw in range(200):
+            raw = rng.integers(0, 256, size=rows * cols // per * bsz, dtype=np.uint8).reshape(-1, bsz)
+            for n, off in enumerate(fields):
+                sel = scales[(np.arange(raw.shape[0]) + 3 * n) % len(scales)]      # (dmin walks the list three entries ahead of d)
+                raw[:, off] = (sel & 0xFF).astype(np.uint8)
+                raw[:, off + 1] = (sel >> 8).astype(np.uint8)
+            raw = raw.reshape(-1)
+            x = rng.standard_normal(cols, dtype=np.float32)
+            want = orc.matmul(raw, t, x, rows, cols)
+            truth = em.DECODERS[kind](raw, rows * cols // per).reshape(rows, cols) @ x.astype(np.float64)
+            if np.all(np.abs(want - truth) <= 5e-6 * (1 + np.abs(truth))):
+                break
+        else:
+            raise AssertionError(f"{kind}: no well-conditioned draw")
+        assert np.all(np.isfinite(want))
+        got = hip.op_matmul(raw, t, x, rows, cols)
+        err = np.abs(got - want) / (1 + np.abs(want))
+        print(f"{kind}: draw {draw}, max err {err.max():.2e} of 2e-5")
+        assert err.max() <= 2e-5, (kind, err.max(), int(err.argmax()))
+        zero = hip.op_matmul(raw, t, np.zeros(cols, np.float32), rows, cols)
+        assert np.all(zero == 0), kind
 
 
 def test_gemv_inf_and_nan_scales_follow_the_reference(hip, orc):

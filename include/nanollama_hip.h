@@ -104,6 +104,22 @@ NL_API int nl_destroy(nl_handle h);
  * for the n listed token ids.  values: [n][dim] float32, or raw IEEE binary16 when is_f16.  May be called before or
  * after nl_finalize; n == 0 removes it. */
 NL_API int nl_set_gamma(nl_handle h, const int32_t *indices, int n, const void *values, int is_f16);
+/* Voices: one base, many personalities.  A handle holds up to NL_MAX_VOICES gamma essences and every KV stream is bound to
+ * one of them; each row of a batched or mixed step takes the gamma of its own stream's voice.
+ *   nl_set_voice    voice 0 is nl_set_gamma's (the call IS nl_set_gamma then); voices 1 .. NL_MAX_VOICES - 1 take the same
+ *                   arguments and rules (ids outside [0, vocab) dropped, f32 or f16 values, before or after nl_finalize,
+ *                   n == 0 removes the voice).  Removing or redefining a voice a stream is bound to: NL_ERR_STATE.
+ *   nl_stream_voice binds a stream (every stream starts on voice 0; binding to 0 is legal with or without a gamma).  The
+ *                   binding outlives nl_reset; rebinding in the middle of a sequence affects the tokens embedded afterwards.
+ *                   Voice or stream out of range, or a voice that is not defined: NL_ERR_INVALID.
+ *   nl_voice_info   the voice `stream` is bound to and the number of voices (0 included) that hold a table.
+ * A stream bound to voice v computes, on every entry point, exactly what a handle whose nl_set_gamma received v's data
+ * computes.  Defining and binding are writes into a device directory the embedding kernels read: neither re-captures a
+ * graph (the first definition on a handle excepted).  On a group handle both calls reach every rank. */
+#define NL_MAX_VOICES 64   /* a decode batch has at most 64 rows: every row may have its own */
+NL_API int nl_set_voice(nl_handle h, int voice, const int32_t *indices, int n, const void *values, int is_f16);
+NL_API int nl_stream_voice(nl_handle h, int stream, int voice);
+NL_API int nl_voice_info(nl_handle h, int stream, int *voice, int *n_defined);
 NL_API const char *nl_last_error(nl_handle h); /* h may be NULL: last create error */
 
 /* == Reset (go/model.go:623-631) ========================================== */

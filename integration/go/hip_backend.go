@@ -139,6 +139,9 @@ func (m *LlamaModel) resetHIP() {
 
 // applyGammaHIP hands the gamma essence (go/gamma.go, go/main.go:70-83) to the device: Forward adds
 // gamma[token] to the embedding row there (go/model.go:503-505).
+// This is voice 0 of the handle.  Further essences on the same weights go in through nl_set_voice(h, v, ...) with the same
+// arguments, and nl_stream_voice(h, 0, v) -- called under the server's generation mutex before Generate -- makes stream 0
+// speak as voice v from the next token on; this shim keeps the Go host's one gamma per process and calls neither.
 func (m *LlamaModel) applyGammaHIP(indices []int32, values []float32) error {
 	var ip *C.int32_t
 	var vp unsafe.Pointer

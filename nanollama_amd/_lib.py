@@ -17,6 +17,7 @@ NL_P2P_HANDLE_BYTES = 64
 NL_FLAG_NO_GRAPH = 1
 NL_FLAG_LOCAL_GROUP = 2
 NL_FLAG_GROUP_FUSED = 4
+NL_MAX_VOICES = 64
 
 STATUS = {0: "NL_OK", -1: "NL_ERR_INVALID", -2: "NL_ERR_UNSUPPORTED", -3: "NL_ERR_HIP", -4: "NL_ERR_STATE",
           -5: "NL_ERR_MISSING", -6: "NL_ERR_COMM"}
@@ -92,7 +93,7 @@ EXPORTS = ["nl_build_info", "nl_set_gamma", "nl_abi_version", "nl_device_count",
            "nl_comm_init", "nl_group_forward", "nl_debug_stamps", "nl_sample_decode", "nl_op_sample", "nl_p2p_export",
            "nl_p2p_import", "nl_p2p_info", "nl_p2p_loopback", "nl_op_exp", "nl_plan_info", "nl_persist_info", "nl_create_group", "nl_host_logits",
            "nl_op_gran16_soak", "nl_forward_batch_sample", "nl_op_sample_rows", "nl_forward_mixed", "nl_forward_mixed_sample",
-           "nl_mixed_capacity", "nl_score", "nl_op_score_rows"]
+           "nl_mixed_capacity", "nl_score", "nl_op_score_rows", "nl_set_voice", "nl_stream_voice", "nl_voice_info"]
 
 
 def lib():
@@ -111,6 +112,9 @@ def lib():
     L.nl_finalize.argtypes = [vp]
     L.nl_destroy.argtypes = [vp]
     L.nl_set_gamma.argtypes = [vp, C.POINTER(C.c_int32), i32, vp, i32]
+    L.nl_set_voice.argtypes = [vp, i32, C.POINTER(C.c_int32), i32, vp, i32]
+    L.nl_stream_voice.argtypes = [vp, i32, i32]
+    L.nl_voice_info.argtypes = [vp, i32, ip, ip]
     L.nl_last_error.restype = C.c_char_p
     L.nl_last_error.argtypes = [vp]
     L.nl_reset.argtypes = [vp, i32]

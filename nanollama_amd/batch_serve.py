@@ -23,7 +23,9 @@ its final prompt token joins as an output row (it does not count against N) and 
 requests that are already decoding get a token in every step instead of waiting for whole prompts.
 
 Settings per request follow go/serve.go:94-103 (temperature, max_tokens and top_k come from the request when > 0); top_p,
-rep_penalty and rep_window are the server's.  Each request samples from its own generator, seeded from the scheduler's
+rep_penalty and rep_window are the server's.  A request may name one of the model's voices (nl_set_voice): the worker binds
+the stream it gives the request -- or the score job -- to that voice (nl_stream_voice; none named: voice 0) before the first
+step that carries the stream's rows, so the rows of one step each take their own voice's gamma.  Each request samples from its own generator, seeded from the scheduler's
 (seeded by --seed) in admission order, and draws a uniform only while its temperature is > 0, as Engine does.
 """
 from __future__ import annotations
@@ -57,6 +59,7 @@ class RequestError(Exception):
 class _Request:
     tokens: List[int]
     params: GenParams
+    voice: int = 0
     done: threading.Event = field(default_factory=threading.Event)
     text: str = ""
     error: Optional[RequestError] = None
@@ -66,6 +69,7 @@ class _Request:
 class _ScoreJob:
     ids: List[int]
     n_context: int
+    voice: int = 0
     done: threading.Event = field(default_factory=threading.Event)
     result: Optional[ScoreResult] = None
     error: Optional[RequestError] = None
@@ -118,14 +122,25 @@ class BatchScheduler:
         self._worker.start()
 
     # ---- callers (any thread) ----
-    def generate_quiet(self, prompt: str, params: GenParams) -> str:
-        """GenerateQuiet (go/main.go:233-291) as one row of the shared batch; blocks until the request is done.
-        Raises RequestError (status 400 / 500)."""
+    def _check_voice(self, voice: int) -> int:
+        if voice and int(voice) not in (getattr(self.model, "voices", None) or {}).values():
+            raise RequestError(400, f"unknown voice id {voice}")
+        return int(voice)
+
+    def _bind(self, stream: int, voice: int) -> None:
+        """The worker, before the first step with rows of `stream`: the stream speaks as `voice`.  A model without named
+        voices has every stream on voice 0 for good."""
+        if getattr(self.model, "voices", None):
+            self.model.stream_voice(stream, voice)
+
+    def generate_quiet(self, prompt: str, params: GenParams, voice: int = 0) -> str:
+        """GenerateQuiet (go/main.go:233-291) as one row of the shared batch, in the voice with id `voice` (model.voices; 0: the
+        default); blocks until the request is done.  Raises RequestError (status 400 / 500)."""
         if not params.top_p > 0:
             raise RequestError(400, f"top_p must be > 0, got {params.top_p}")
         if params.temperature > 0 and params.top_p >= 1.0 and not 1 <= params.top_k <= MAX_TOP_K:
             raise RequestError(400, f"top_k must be in [1, {MAX_TOP_K}] for batched sampling, got {params.top_k}")
-        req = _Request(self.tokenizer.encode(prompt, True), params)
+        req = _Request(self.tokenizer.encode(prompt, True), params, self._check_voice(voice))
         with self._cv:
             if self._closed:
                 raise RequestError(500, "scheduler closed")
@@ -136,9 +151,10 @@ class BatchScheduler:
             raise req.error
         return req.text
 
-    def score(self, ids: List[int], n_context: int = 1) -> ScoreResult:
-        """score.score_ids(model, ids, a free stream, n_context) on the worker; blocks until done.  Raises RequestError (500)."""
-        job = _ScoreJob([int(t) for t in ids], int(n_context))
+    def score(self, ids: List[int], n_context: int = 1, voice: int = 0) -> ScoreResult:
+        """score.score_ids(model, ids, a free stream, n_context) on the worker, in voice `voice`; blocks until done.
+        Raises RequestError (400: unknown voice id; 500)."""
+        job = _ScoreJob([int(t) for t in ids], int(n_context), self._check_voice(voice))
         with self._cv:
             if self._closed:
                 raise RequestError(500, "scheduler closed")
@@ -168,6 +184,7 @@ class BatchScheduler:
     def _score(self, job: _ScoreJob, stream: int, free: List[int]) -> None:
         try:
             self.model.reset(stream)
+            self._bind(stream, job.voice)
             job.result = score_ids(self.model, job.ids, stream, job.n_context)
         except Exception as exc:                        # engine error: this job fails, the scheduler goes on
             free.append(stream)
@@ -190,6 +207,7 @@ class BatchScheduler:
             return
         try:
             self.model.reset(stream)
+            self._bind(stream, req.voice)
             if n_prompt > 1 and not self.prefill_chunk:
                 self.model.prefill(req.tokens[:n_prompt - 1], pos0=0, stream=stream, want_logits=False)
         except Exception as exc:                        # engine error: this request fails, the scheduler goes on

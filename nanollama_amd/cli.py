@@ -5,6 +5,9 @@
     python -m nanollama_amd --model m.gguf --serve --port 8080         (HTTP: GET /, POST /chat, POST /score, GET /health)
     python -m nanollama_amd --model m.gguf --score text.txt            (log-probability, perplexity, bits per byte of a text)
     python -m nanollama_amd --model m.gguf --serve --parallel 16 --prefill-chunk 64   (batched server, chunked admission)
+    python -m nanollama_amd --model m.gguf --voice leo=leo.npz --voice yent=yent.npz --serve --parallel 16
+                                                                        (one base, several gamma essences: "voice" per request)
+    python -m nanollama_amd --model m.gguf --voice leo=leo.npz --use-voice leo --prompt "Hello"
 """
 from __future__ import annotations
 
@@ -23,6 +26,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="nanollama", description="nanollama inference on MI355X (GGUF in, text out)")
     ap.add_argument("--model", default="", help="Path to GGUF model file (required)")
     ap.add_argument("--gamma", default="", help="Path to gamma NPZ file (optional, personality)")
+    ap.add_argument("--voice", action="append", default=[], metavar="NAME=PATH",
+                    help="a named gamma NPZ next to --gamma (repeatable, at most 63): /chat and /score requests pick one with "
+                         '"voice": NAME, other runs with --use-voice NAME; --gamma stays the default voice')
+    ap.add_argument("--use-voice", default="", metavar="NAME",
+                    help="with --prompt, --interactive, --score or stdin: generate / score as the --voice of this name")
     ap.add_argument("--prompt", default="", help="Prompt text (if empty, reads from stdin)")
     ap.add_argument("--max-tokens", type=int, default=256, help="Maximum tokens to generate")
     ap.add_argument("--temp", type=float, default=0.8, help="Sampling temperature (0 = greedy)")
@@ -72,6 +80,54 @@ def run_score(eng, path: str, out=None) -> None:
     r = score_text(eng.model, eng.tokenizer, text)
     dt = time.perf_counter() - t0
     print(f"tokens {r.n_tokens}  nll {r.nll:.6f}  ppl {r.ppl:.4f}  bpb {r.bpb:.6f}  {r.n_tokens / dt if dt > 0 else 0.0:.1f} tokens/s", file=out)
+
+
+MAX_NAMED_VOICES = 63        # voices 1 .. NL_MAX_VOICES - 1 (voice 0 is --gamma)
+
+
+def parse_voices(specs) -> list:
+    """--voice NAME=PATH ...: [(name, path)], names unique and non-empty."""
+    out = []
+    for spec in specs:
+        name, sep, path = spec.partition("=")
+        name = name.strip()
+        if not sep or not name or not path:
+            raise RuntimeError(f"--voice takes NAME=PATH, got {spec!r}")
+        if name in [n for n, _ in out]:
+            raise RuntimeError(f"--voice {name!r} is given twice")
+        out.append((name, path))
+    if len(out) > MAX_NAMED_VOICES:
+        raise RuntimeError(f"at most {MAX_NAMED_VOICES} --voice entries, got {len(out)}")
+    return out
+
+
+def check_voices(args) -> None:
+    """--voice / --use-voice: the specs parse, and --use-voice names one of them (a server's requests name their own)."""
+    names = [n for n, _ in parse_voices(args.voice)]
+    if args.use_voice and args.serve:
+        raise RuntimeError('--use-voice is not for --serve: a request names its voice ("voice": NAME)')
+    if args.use_voice and args.use_voice not in names:
+        raise RuntimeError(f"--use-voice {args.use_voice!r} is not among the --voice names ({', '.join(names) or 'none given'})")
+
+
+def load_voices(model, specs) -> None:
+    """Define voices 1, 2, ... from the --voice files (gamma.load_gamma) and record their names in model.voices."""
+    from .gamma import load_gamma
+    for vid, (name, path) in enumerate(parse_voices(specs), start=1):
+        try:
+            ge = load_gamma(path)
+        except ValueError as exc:
+            raise RuntimeError(f"--voice {name}: {exc}") from exc
+        if ge.embed_dim != model.config.embed_dim:
+            raise RuntimeError(f"--voice {name}: gamma embed_dim {ge.embed_dim} != model dim {model.config.embed_dim}")
+        if ge.num_tokens == 0:
+            raise RuntimeError(f"--voice {name}: the file lists no tokens")
+        try:
+            model.set_voice(vid, ge.indices, ge.values)
+        except ValueError as exc:
+            raise RuntimeError(f"--voice {name}: {exc}") from exc
+        model.voices[name] = vid
+        print(f"[nanollama] voice {name!r} loaded: {ge.num_tokens} tokens modified")
 
 
 MAX_MIXED_ROWS = 512         # rows of one mixed step (nl_mixed_capacity reports the handle's own limit, at most this)
@@ -143,6 +199,9 @@ def load_engine(args) -> TextEngine:
                 print(f"[nanollama] personality loaded: {ge.num_tokens} tokens modified")
         except ValueError as exc:
             print(f"warning: failed to load gamma: {exc}", file=sys.stderr)
+    load_voices(model, args.voice)
+    if args.use_voice:
+        model.stream_voice(0, model.voices[args.use_voice])
     tok = Tokenizer(g.meta, verbose=True)
     eng = TextEngine(model, tok, rep_penalty=args.rep_penalty, rep_window=args.rep_window, seed=args.seed)
     print("[nanollama] ready — %dM params, %d layers, %d dim" % (estimate_params(model.config) // 1_000_000,
@@ -167,6 +226,8 @@ def run_repl(eng: TextEngine, params: GenParams) -> None:
             print(f"Model: {c.num_layers} layers, {c.embed_dim} dim, {c.num_heads} heads, {c.num_kv_heads} kv_heads, {c.vocab_size} vocab")
             print("Params: ~%dM" % (estimate_params(c) // 1_000_000))
             print(f"Gamma: {eng.model.gamma is not None}")
+            if getattr(eng.model, "voices", None):
+                print(f"Voices: {', '.join(eng.model.voices)}")
             print(f"Flags: qk_norm={c.qk_norm} rope_conjugate={c.rope_conjugate}")
             continue
         eng.generate(text, params, stream=sys.stdout)
@@ -186,6 +247,7 @@ def main(argv=None) -> int:
         check_parallel(args)
         check_prefill_chunk(args)
         check_score(args)
+        check_voices(args)
         eng = load_engine(args)
         if args.prefill_chunk > 0:
             check_prefill_chunk(args, eng.model.mixed_capacity[0])

@@ -171,8 +171,7 @@ struct BEmbedParams {
     int wtype, dim;
     const int *tokens;
     float *x;  // [N][dim]
-    const int *gamma_row;
-    const float *gamma_val;
+    const VoiceDir *voices;   // gamma of the voice row r's stream is bound to (stream[r]); nullptr = no gamma
     // optional (decode batches / short prompts on dgemm_kernel): the token's RoPE rows and cache row offset, QGemmParams::Rope::tcos ...
     const int *pos, *stream;
     const float *rope_cos, *rope_sin;
@@ -193,10 +192,10 @@ __global__ void bembed_kernel(BEmbedParams P) {
         }
         if (threadIdx.x == 0) P.tkv[blockIdx.x] = (long long)strm * P.kv_stream_stride + (long long)pos * P.hd;
     }
-    const int gr = P.gamma_row ? P.gamma_row[token] : -1;
+    const float *gam = voice_gamma(P.voices, P.voices ? sload_i32(P.stream + blockIdx.x) : 0, token, P.dim);
     for (int i = threadIdx.x; i < P.dim; i += blockDim.x) {
         float v = embed_value(P.table, P.wtype, P.dim, token, i);
-        if (gr >= 0) v += P.gamma_val[(long long)gr * P.dim + i];
+        if (gam) v += gam[i];
         x[i] = v;
     }
 }

@@ -38,7 +38,7 @@
 #include <thread>
 #include <vector>
 
-namespace { void samp_free(nl::SampScratch &s); }
+namespace { void samp_free(nl::SampScratch &s); int voice_dir_alloc(nl_engine *e); }
 
 using namespace nl;
 
@@ -290,8 +290,15 @@ struct nl_engine {
     bool have_output = false;
     float *output_norm = nullptr;
 
-    int *gamma_row = nullptr;      // [vocab] -> row of gamma_val or -1 (go/gamma.go IndexMap)
-    float *gamma_val = nullptr;    // [n][dim]
+    // Voices (nl_set_voice / nl_stream_voice; voice 0 is nl_set_gamma's): the device directory (VoiceDir, nl_kernels.h) lives
+    // from nl_create to nl_destroy at one address; these are its host mirror and the owners of the tables it points at
+    VoiceDir *vdir = nullptr;
+    bool vdir_on = false;          // the embedding launches carry vdir; false: nullptr, the no-gamma path (no voice ever defined)
+    int *voice_row[VOICE_MAX] = {};     // [vocab] -> row of voice_val or -1 (go/gamma.go IndexMap)
+    float *voice_val[VOICE_MAX] = {};   // [n][dim]
+    size_t voice_bytes[VOICE_MAX] = {};
+    std::vector<int> stream_voice;      // [max_streams]
+    const VoiceDir *voices() const { return vdir_on ? vdir : nullptr; }
     float *rope_cos = nullptr, *rope_sin = nullptr;
     float *x[2] = {nullptr, nullptr};
     float *qbuf = nullptr, *part_o = nullptr, *part_ml = nullptr, *hb = nullptr, *ar = nullptr, *logits = nullptr;
@@ -818,7 +825,7 @@ void build_plan_blocks(nl_engine *e, std::vector<Op> &plan) {
     const nl_config &c = e->cfg;
     const int nslices = e->Is / FFN_SLICE;
     {
-        EmbedParams P{e->embd_raw, e->embd_type, c.dim, e->ctl, e->x[0], e->gamma_row, e->gamma_val, e->tick};
+        EmbedParams P{e->embd_raw, e->embd_type, c.dim, e->ctl, e->x[0], e->voices(), e->tick};
         e->plan_embed = P;
         plan.push_back({K_EMBED, 0, nullptr, 0, [P](hipStream_t st) {
                                hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, P);
@@ -914,7 +921,7 @@ void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = fal
     int seam = 0;
 
     {
-        EmbedParams P{e->embd_raw, e->embd_type, c.dim, e->ctl, e->x[0], e->gamma_row, e->gamma_val, p2p ? e->p2p.epoch : e->tick};
+        EmbedParams P{e->embd_raw, e->embd_type, c.dim, e->ctl, e->x[0], e->voices(), p2p ? e->p2p.epoch : e->tick};
         e->plan_embed = P;
         plan.push_back({K_EMBED, 0, nullptr, 0, [P](hipStream_t st) {
                                hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, P);
@@ -1564,12 +1571,16 @@ int pd_build(nl_engine *e) {
     HIPCK(e, hipHostMalloc((void **)&d.h_status, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
     *d.h_status = 0;
     // (the instantiations pd_shape_ok admits)
-    const void *kfn = c.dim == 576 ? (c.n_kv_heads == 9 ? reinterpret_cast<const void *>(pd_decode_kernel<18, 48, 9>) : reinterpret_cast<const void *>(pd_decode_kernel<18, 48, 3>))
-                                   : (c.n_kv_heads == 4 ? reinterpret_cast<const void *>(pd_decode_kernel<8, 16, 4>) : reinterpret_cast<const void *>(pd_decode_kernel<8, 16, 2>));
-    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_lds_bytes()) != hipSuccess) {
-        (void)hipGetLastError();
-        d.candidate = false;
-        return NL_OK;
+#define PD_FN(NB, NBI, KVH) { reinterpret_cast<const void *>(pd_decode_kernel<NB, NBI, KVH, false>), reinterpret_cast<const void *>(pd_decode_kernel<NB, NBI, KVH, true>) }
+    const void *k576_9[2] = PD_FN(18, 48, 9), *k576_3[2] = PD_FN(18, 48, 3), *k256_4[2] = PD_FN(8, 16, 4), *k256_2[2] = PD_FN(8, 16, 2);
+#undef PD_FN
+    const void *const *kfn = c.dim == 576 ? (c.n_kv_heads == 9 ? k576_9 : k576_3) : (c.n_kv_heads == 4 ? k256_4 : k256_2);
+    for (int gm = 0; gm < 2; gm++) {       // (without and with a gamma row in the embedding)
+        if (hipFuncSetAttribute(kfn[gm], hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_lds_bytes()) != hipSuccess) {
+            (void)hipGetLastError();
+            d.candidate = false;
+            return NL_OK;
+        }
     }
     d.session_on = e->knobs.persist_session && d.d_mail;
     d.max_pos = std::min(e->knobs.persist_max_pos, c.seq_len);
@@ -1579,7 +1590,7 @@ int pd_build(nl_engine *e) {
 }
 
 bool pd_usable(const nl_engine *e, int pos, int n) {
-    return e->pd.ready && !e->pd.retired && n > 0 && pos + n <= e->pd.max_pos && !e->gamma_row && e->G == 1;
+    return e->pd.ready && !e->pd.retired && n > 0 && pos + n <= e->pd.max_pos && e->G == 1;
 }
 
 // One launch = n greedy tokens from (token, pos); ids land in e->ids.  The caller synchronises and then asks pd_take_timeout.
@@ -1607,16 +1618,22 @@ int pd_launch(nl_engine *e, int stream, int token, int pos, int n, float *host_l
     P.wimg = d.wimg; P.simg = d.simg; P.lmimg = d.lmimg; P.lmsimg = d.lmsimg;
     P.norms = d.norms;
     P.embd_raw = e->pd.embd_q8 ? e->pd.embd_q8 : e->embd_raw;
+    // the launch serves ONE stream: its voice's table goes in by value (a rebind or a definition ends a resident session first)
+    P.gamma_row = e->voice_row[e->stream_voice[stream]]; P.gamma_val = e->voice_val[e->stream_voice[stream]];
     P.rope_cos = e->rope_cos; P.rope_sin = e->rope_sin;
     P.kcache = e->kcache + (long long)stream * e->kv_stream_stride; P.vcache = e->vcache + (long long)stream * e->kv_stream_stride;
     P.kv_layer_stride = e->kv_layer_stride;
     P.gx = d.gx; P.gqkv = d.gqkv; P.go = d.go; P.gxp = d.gxp; P.gh = d.gh; P.gam = d.gam; P.gpart = d.gpart;
     P.ids_out = e->ids; P.logits = e->logits; P.host_logits = host_logits;
     P.status = d.status; P.host_status = d.h_status; P.dbg = d.dbg;
-    if (c.dim == 576 && c.n_kv_heads == 9) hipLaunchKernelGGL((pd_decode_kernel<18, 48, 9>), dim3(PD_GRID), dim3(PD_THREADS), pd_lds_bytes(), e->stream, P);
-    else if (c.dim == 576) hipLaunchKernelGGL((pd_decode_kernel<18, 48, 3>), dim3(PD_GRID), dim3(PD_THREADS), pd_lds_bytes(), e->stream, P);
-    else if (c.n_kv_heads == 4) hipLaunchKernelGGL((pd_decode_kernel<8, 16, 4>), dim3(PD_GRID), dim3(PD_THREADS), pd_lds_bytes(), e->stream, P);
-    else hipLaunchKernelGGL((pd_decode_kernel<8, 16, 2>), dim3(PD_GRID), dim3(PD_THREADS), pd_lds_bytes(), e->stream, P);
+#define PD_LAUNCH(NB, NBI, KVH) do { \
+        if (P.gamma_row) hipLaunchKernelGGL((pd_decode_kernel<NB, NBI, KVH, true>), dim3(PD_GRID), dim3(PD_THREADS), pd_lds_bytes(), e->stream, P); \
+        else hipLaunchKernelGGL((pd_decode_kernel<NB, NBI, KVH, false>), dim3(PD_GRID), dim3(PD_THREADS), pd_lds_bytes(), e->stream, P); } while (0)
+    if (c.dim == 576 && c.n_kv_heads == 9) PD_LAUNCH(18, 48, 9);
+    else if (c.dim == 576) PD_LAUNCH(18, 48, 3);
+    else if (c.n_kv_heads == 4) PD_LAUNCH(8, 16, 4);
+    else PD_LAUNCH(8, 16, 2);
+#undef PD_LAUNCH
     HIPCK(e, hipGetLastError());
     d.launches++; d.tokens += n;
     return NL_OK;
@@ -2137,7 +2154,7 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     }
     LCK(hipMemcpyAsync(b.tok, b.h_meta, (size_t)5 * b.cap * 4, hipMemcpyHostToDevice, st));
     {
-        BEmbedParams P{e->embd_raw, e->embd_type, D, b.tok, b.x, e->gamma_row, e->gamma_val,
+        BEmbedParams P{e->embd_raw, e->embd_type, D, b.tok, b.x, e->voices(),
                        b.pos, b.stream, e->rope_cos, e->rope_sin, b.tcos, b.tsin, b.tkv, hd / 2, hd, e->kv_stream_stride};
         hipLaunchKernelGGL(bembed_kernel, dim3(n), dim3(256), 0, st, P);
         LCK(hipGetLastError());
@@ -2610,6 +2627,7 @@ int nl_create(const nl_config *cfg, nl_handle *out) {
         delete e;
         return NL_ERR_HIP;
     }
+    e->stream_voice.assign(c.max_streams, 0);     // every stream starts on voice 0
     *out = e;
     return NL_OK;
 }
@@ -2957,6 +2975,7 @@ int nl_finalize(nl_handle e) {
     e->hw.assign(c.max_streams, 0);
     e->ids_cap = c.seq_len + 1;
     HIPCK(e, dalloc(&e->ctl, (size_t)CTL_WORDS, &e->bytes_state));
+    if (int rc = voice_dir_alloc(e)) return rc;
     HIPCK(e, dalloc(&e->ids, (size_t)e->ids_cap, &e->bytes_state));
     HIPCK(e, dalloc(&e->result, (size_t)1, &e->bytes_state));
     e->amax_slots = ((e->Vs + TR - 1) / TR) + 64;  // >= one slot per wave of LM-head rows for any tw
@@ -3204,33 +3223,41 @@ int nl_finalize(nl_handle e) {
 
 // Gamma essence (go/gamma.go): embed[token] += gamma[token] for the listed tokens (go/model.go:503-505).
 // indices: n token ids; values: [n][dim] float32, or raw IEEE binary16 when is_f16.  n == 0 clears it.
-int nl_set_gamma(nl_handle e, const int32_t *indices, int n, const void *values, int is_f16) {
-    if (e && e->grp) {
-        // one rank after the other, as nl_finalize: the body allocates, frees and re-captures graphs, none of which may overlap
-        // another thread's capture.  A rank that fails keeps its old table (the body only swaps on success); the ranks before it
-        // are put back to "no gamma" and the call reports the error, so the ranks never decode with different embeddings.
-        for (size_t r = 0; r < e->grp->members.size(); r++) {
-            const int rc = nl_set_gamma(e->grp->members[r], indices, n, values, is_f16);
-            if (rc != NL_OK) {
-                e->err = "rank " + std::to_string(r) + ": " + e->grp->members[r]->err;
-                for (size_t q = 0; q <= r; q++) (void)nl_set_gamma(e->grp->members[q], nullptr, 0, nullptr, 0);
-                for (size_t q = r + 1; q < e->grp->members.size(); q++) (void)nl_set_gamma(e->grp->members[q], nullptr, 0, nullptr, 0);
-                return rc;
-            }
-        }
-        return NL_OK;
-    }
+// One rank's table of one voice (voice 0: nl_set_gamma, 1 .. 63: nl_set_voice).  The embedding launches hold the address of
+// the voice directory, never a table's, so a definition is a write into the directory behind a synchronise: plans and graphs
+// stay as they are -- except when the directory goes on or off duty (vdir_on: the no-gamma path passes nullptr), and in
+// nl_set_gamma, which rebuilds them as it always did.
+static_assert(VOICE_MAX == NL_MAX_VOICES, "the device directory holds every voice of the ABI");
+namespace {
+// The voice directory (no voice defined, every stream on voice 0): allocated by nl_finalize, or by the first voice call when
+// that comes earlier -- not by nl_create, which must leave the device alone between the stream creations of a group's ranks
+// (the ranks of a group on one device each need a hardware queue of their own).
+int voice_dir_alloc(nl_engine *e) {
+    if (e->vdir) return NL_OK;
+    const size_t vbytes = sizeof(VoiceDir) + (size_t)(e->cfg.max_streams - 1) * sizeof(int);
+    HIPCK(e, hipMalloc((void **)&e->vdir, vbytes));
+    HIPCK(e, hipMemset(e->vdir, 0, vbytes));
+    e->bytes_state += vbytes;
+    return NL_OK;
+}
+
+int voice_define(nl_engine *e, int voice, const int32_t *indices, int n, const void *values, int is_f16, const char *who) {
     if (!e || n < 0 || (n > 0 && (!indices || !values))) return NL_ERR_INVALID;
     const nl_config &c = e->cfg;
     std::lock_guard<std::mutex> setup(g_setup_mu);      // (allocations, frees and graph captures below)
     HIPCK(e, hipSetDevice(e->dev));
     if (int qrc = pd_session_close(e)) return qrc;
     HIPCK(e, hipStreamSynchronize(e->stream));
-    // Build and upload the new tables BEFORE touching the old ones: the plan closures and captured graphs hold the
-    // old device pointers until they are rebuilt below, so no error path may leave them dangling.  Indices outside
-    // [0, vocab) are dropped: the Go side keeps a map keyed by token id (go/gamma.go IndexMap) that such ids never hit.
+    if (int rc = voice_dir_alloc(e)) return rc;
+    if (voice > 0)
+        for (int st = 0; st < c.max_streams; st++)
+            if (e->stream_voice[st] == voice) return e->fail(NL_ERR_STATE, "%s: stream %d is bound to voice %d", who, st, voice);
+    // Build and upload the new tables BEFORE touching the old ones: no error path may leave the directory pointing at
+    // freed memory.  Indices outside [0, vocab) are dropped: the Go side keeps a map keyed by token id (go/gamma.go IndexMap)
+    // that such ids never hit.
     int *new_row = nullptr;
     float *new_val = nullptr;
+    size_t new_bytes = 0;
     if (n > 0) {
         std::vector<int> rowmap(c.vocab, -1);
         for (int i = 0; i < n; i++)
@@ -3240,30 +3267,120 @@ int nl_set_gamma(nl_handle e, const int32_t *indices, int n, const void *values,
             const uint16_t *hp = (const uint16_t *)values;
             for (size_t i = 0; i < vals.size(); i++) vals[i] = __half2float(__ushort_as_half(hp[i]));
         } else memcpy(vals.data(), values, vals.size() * 4);
-        hipError_t s = dalloc(&new_row, (size_t)c.vocab);
-        if (s == hipSuccess) s = dalloc(&new_val, vals.size());
+        hipError_t s = dalloc(&new_row, (size_t)c.vocab, &new_bytes);
+        if (s == hipSuccess) s = dalloc(&new_val, vals.size(), &new_bytes);
         if (s == hipSuccess) s = hipMemcpy(new_row, rowmap.data(), (size_t)c.vocab * 4, hipMemcpyHostToDevice);
         if (s == hipSuccess) s = hipMemcpy(new_val, vals.data(), vals.size() * 4, hipMemcpyHostToDevice);
+        const VoiceDir::Voice ent{new_row, new_val};
+        if (s == hipSuccess) s = hipMemcpy(&e->vdir->voice[voice], &ent, sizeof(ent), hipMemcpyHostToDevice);
         if (s != hipSuccess) {
             if (new_row) (void)hipFree(new_row);
             if (new_val) (void)hipFree(new_val);
-            return e->fail(NL_ERR_HIP, "nl_set_gamma: %s", hipGetErrorString(s));   // old gamma still in force
+            return e->fail(NL_ERR_HIP, "%s: %s", who, hipGetErrorString(s));   // the old table is still in force
         }
+    } else {
+        const VoiceDir::Voice none{nullptr, nullptr};
+        hipError_t s = hipMemcpy(&e->vdir->voice[voice], &none, sizeof(none), hipMemcpyHostToDevice);
+        if (s != hipSuccess) return e->fail(NL_ERR_HIP, "%s: %s", who, hipGetErrorString(s));
     }
-    int *old_row = e->gamma_row;
-    float *old_val = e->gamma_val;
-    e->gamma_row = new_row;
-    e->gamma_val = new_val;
-    destroy_step_graphs(e);   // (they hold the old tables too)
-    if (e->finalized) {  // the launch closures hold the old pointers: rebuild plans and graphs
-        destroy_samp_graphs(e);
-        if (build_all(e)) {   // the rebuilt eager plans are valid; only the graphs were lost
-            for (auto &S : e->ps) destroy_graphs(S);
-            e->use_graph = false;
+    int *old_row = e->voice_row[voice];
+    float *old_val = e->voice_val[voice];
+    e->bytes_state += new_bytes;
+    e->bytes_state -= e->voice_bytes[voice];
+    e->voice_row[voice] = new_row;
+    e->voice_val[voice] = new_val;
+    e->voice_bytes[voice] = new_bytes;
+    // on duty from the first definition; off again only when nl_set_gamma clears voice 0 and no other voice is left
+    bool any = false;
+    for (int v = 0; v < VOICE_MAX; v++) any = any || e->voice_row[v];
+    const bool on = voice == 0 ? any : true;
+    const bool rebuild = voice == 0 || on != e->vdir_on;
+    e->vdir_on = on;
+    if (rebuild) {
+        destroy_step_graphs(e);   // (they hold the launches' arguments)
+        if (e->finalized) {  // the launch closures hold the directory's address or nullptr: rebuild plans and graphs
+            destroy_samp_graphs(e);
+            if (build_all(e)) {   // the rebuilt eager plans are valid; only the graphs were lost
+                for (auto &S : e->ps) destroy_graphs(S);
+                e->use_graph = false;
+            }
         }
     }
     if (old_row) (void)hipFree(old_row);   // nothing references the old tables any more
     if (old_val) (void)hipFree(old_val);
+    return NL_OK;
+}
+
+// a group call: one rank after the other, as nl_finalize (the body allocates, frees and may re-capture graphs, none of which
+// may overlap another thread's capture).  A rank that fails keeps its old table (the body only swaps on success); the voice
+// is then cleared on every rank and the call reports the error, so the ranks never decode with different embeddings.
+int voice_define_group(nl_engine *e, int voice, const int32_t *indices, int n, const void *values, int is_f16, const char *who) {
+    for (size_t r = 0; r < e->grp->members.size(); r++) {
+        const int rc = voice_define(e->grp->members[r], voice, indices, n, values, is_f16, who);
+        if (rc != NL_OK) {
+            e->err = "rank " + std::to_string(r) + ": " + e->grp->members[r]->err;
+            if (rc != NL_ERR_STATE)      // (a bound voice is refused by rank 0 before anything changed)
+                for (nl_engine *m : e->grp->members) (void)voice_define(m, voice, nullptr, 0, nullptr, 0, who);
+            return rc;
+        }
+    }
+    return NL_OK;
+}
+}  // namespace
+
+int nl_set_gamma(nl_handle e, const int32_t *indices, int n, const void *values, int is_f16) {
+    if (e && e->grp) return voice_define_group(e, 0, indices, n, values, is_f16, "nl_set_gamma");
+    return voice_define(e, 0, indices, n, values, is_f16, "nl_set_gamma");
+}
+
+// Voices 1 .. NL_MAX_VOICES - 1: further gamma essences on the same weights, nl_set_gamma's arguments and rules; n == 0
+// removes the voice.  A voice some stream is bound to can be neither removed nor redefined (NL_ERR_STATE).
+int nl_set_voice(nl_handle e, int voice, const int32_t *indices, int n, const void *values, int is_f16) {
+    if (!e) return NL_ERR_INVALID;
+    if (voice == 0) return nl_set_gamma(e, indices, n, values, is_f16);
+    if (voice < 0 || voice >= NL_MAX_VOICES) return e->fail(NL_ERR_INVALID, "nl_set_voice: voice %d out of range", voice);
+    if (e->grp) return voice_define_group(e, voice, indices, n, values, is_f16, "nl_set_voice");
+    return voice_define(e, voice, indices, n, values, is_f16, "nl_set_voice");
+}
+
+// Bind a stream to a defined voice (voice 0 is always legal, gamma or not): the tokens the stream embeds from now on take
+// that voice's gamma.  One word of the directory, written behind a synchronise; it outlives nl_reset.
+int nl_stream_voice(nl_handle e, int stream, int voice) {
+    if (!e) return NL_ERR_INVALID;
+    if (e->grp) {
+        int before = 0;
+        if (nl_voice_info(e, stream, &before, nullptr) != NL_OK) before = 0;
+        for (size_t r = 0; r < e->grp->members.size(); r++) {
+            const int rc = nl_stream_voice(e->grp->members[r], stream, voice);
+            if (rc != NL_OK) {
+                e->err = "rank " + std::to_string(r) + ": " + e->grp->members[r]->err;
+                for (size_t q = 0; q < r; q++) (void)nl_stream_voice(e->grp->members[q], stream, before);
+                return rc;
+            }
+        }
+        return NL_OK;
+    }
+    if (stream < 0 || stream >= e->cfg.max_streams) return e->fail(NL_ERR_INVALID, "stream %d out of range", stream);
+    if (voice < 0 || voice >= NL_MAX_VOICES) return e->fail(NL_ERR_INVALID, "nl_stream_voice: voice %d out of range", voice);
+    if (voice > 0 && !e->voice_row[voice]) return e->fail(NL_ERR_INVALID, "nl_stream_voice: voice %d is not defined", voice);
+    HIPCK(e, hipSetDevice(e->dev));
+    if (int qrc = pd_session_close(e)) return qrc;
+    if (e->stream_voice[stream] == voice) return NL_OK;
+    HIPCK(e, hipStreamSynchronize(e->stream));
+    if (int rc = voice_dir_alloc(e)) return rc;
+    HIPCK(e, hipMemcpy(&e->vdir->stream_voice[stream], &voice, sizeof(int), hipMemcpyHostToDevice));
+    e->stream_voice[stream] = voice;
+    return NL_OK;
+}
+
+int nl_voice_info(nl_handle e, int stream, int *voice, int *n_defined) {
+    if (e && e->grp) return e->grp->members.empty() ? NL_ERR_INVALID : nl_voice_info(e->grp->members[0], stream, voice, n_defined);
+    if (!e) return NL_ERR_INVALID;
+    if (stream < 0 || stream >= e->cfg.max_streams) return e->fail(NL_ERR_INVALID, "stream %d out of range", stream);
+    int nd = 0;
+    for (int v = 0; v < NL_MAX_VOICES; v++) nd += e->voice_row[v] ? 1 : 0;
+    if (voice) *voice = e->stream_voice[stream];
+    if (n_defined) *n_defined = nd;
     return NL_OK;
 }
 
@@ -3294,8 +3411,11 @@ int nl_destroy(nl_handle e) {
         for (float *b : bs) if (b) hipFree(b);
     }
     pd_free(e);
-    if (e->gamma_row) hipFree(e->gamma_row);
-    if (e->gamma_val) hipFree(e->gamma_val);
+    for (int v = 0; v < VOICE_MAX; v++) {
+        if (e->voice_row[v]) hipFree(e->voice_row[v]);
+        if (e->voice_val[v]) hipFree(e->voice_val[v]);
+    }
+    if (e->vdir) hipFree(e->vdir);
     for (void *c : e->arena_chunks) hipFree(c);
     if (e->stage) hipFree(e->stage);
     for (void *p : {(void *)e->sc_targets, (void *)e->sc_argmax, (void *)e->sc_logprob}) if (p) hipFree(p);

@@ -966,14 +966,33 @@ __global__ void __launch_bounds__(512) gemv_kernel(GemvParams P) {
 
 // ------------------------------------------------------------- embedding ---
 
+// Voices: one gamma essence per voice, one voice per stream (nl_set_voice / nl_stream_voice).  The engine keeps ONE directory
+// at a stable device address and hands every embedding launch that address, never a table: defining a voice and binding a
+// stream are plain writes into it, ordered on the engine's stream with the steps, so plans and captured graphs stay valid.
+constexpr int VOICE_MAX = 64;     // == NL_MAX_VOICES
+struct VoiceDir {
+    struct Voice {
+        const int *row;           // [vocab] row in val or -1 (go/gamma.go IndexMap); nullptr = voice not defined
+        const float *val;         // [n][dim]
+    } voice[VOICE_MAX];
+    int stream_voice[1];          // [max_streams] (allocated behind the header)
+};
+// the gamma row added to `token`'s embedding on `stream`, or nullptr
+__device__ __forceinline__ const float *voice_gamma(const VoiceDir *vd, int stream, int token, int dim) {
+    if (!vd) return nullptr;
+    const VoiceDir::Voice V = vd->voice[vd->stream_voice[stream]];
+    if (!V.row) return nullptr;
+    const int gr = V.row[token];
+    return gr >= 0 ? V.val + (long long)gr * dim : nullptr;
+}
+
 struct EmbedParams {
     const uint8_t *table;  // raw GGUF rows
     int wtype, dim;
     const int *ctl;
     float *x;
-    // gamma injection (go/gamma.go:272-290, go/model.go:503-505): embed[token] += gamma[token] for listed tokens
-    const int *gamma_row;     // [vocab] row in gamma_val or -1; nullptr = no gamma
-    const float *gamma_val;   // [n][dim]
+    // gamma injection (go/gamma.go:272-290, go/model.go:503-505): embed[token] += gamma[token] for listed tokens, from
+    const VoiceDir *voices;   // the table of the voice the step's stream (ctl[CTL_STREAM]) is bound to; nullptr = no gamma
     unsigned *epoch;          // tensor-parallel push (nl_p2p.h): forward counter, advanced here once per Forward
 };
 
@@ -1027,16 +1046,16 @@ __device__ __forceinline__ float embed_value(const uint8_t *table, int wtype, in
 __global__ void embed_kernel(EmbedParams P) {
     if (P.epoch && threadIdx.x == 0) *P.epoch = *P.epoch + 1;
     const int token = sload_i32(P.ctl + CTL_TOKEN);
-    const int gr = P.gamma_row ? P.gamma_row[token] : -1;
+    const float *gam = voice_gamma(P.voices, P.voices ? sload_i32(P.ctl + CTL_STREAM) : 0, token, P.dim);
     // four elements per lane and round, their byte loads issued together (clamped index, masked store): one memory
     // latency per round instead of one per element
     for (int i0 = threadIdx.x; i0 < P.dim; i0 += 4 * blockDim.x) {
         float v[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) v[k] = embed_value(P.table, P.wtype, P.dim, token, min(i0 + k * (int)blockDim.x, P.dim - 1));
-        if (gr >= 0) {
+        if (gam) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) v[k] += P.gamma_val[(long long)gr * P.dim + min(i0 + k * (int)blockDim.x, P.dim - 1)];
+            for (int k = 0; k < 4; k++) v[k] += gam[min(i0 + k * (int)blockDim.x, P.dim - 1)];
         }
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -1475,10 +1494,10 @@ __global__ void __launch_bounds__(1024) argmax_embed_kernel(ArgmaxParams P, Embe
     }
     __syncthreads();
     const int token = tok;
-    const int gr = E.gamma_row ? E.gamma_row[token] : -1;
+    const float *gam = voice_gamma(E.voices, E.voices ? E.ctl[CTL_STREAM] : 0, token, E.dim);
     for (int i = tid; i < E.dim; i += blockDim.x) {
         float v = embed_value(E.table, E.wtype, E.dim, token, i);
-        if (gr >= 0) v += E.gamma_val[(long long)gr * E.dim + i];
+        if (gam) v += gam[i];
         E.x[i] = v;
     }
 }

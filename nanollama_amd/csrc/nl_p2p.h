@@ -129,10 +129,10 @@ __global__ void __launch_bounds__(1024) p2p_argmax_kernel(P2PArgmaxParams P) {
     if (!P.E.x) return;
     __syncthreads();
     const int token = tok;
-    const int gr = P.E.gamma_row ? P.E.gamma_row[token] : -1;
+    const float *gam = voice_gamma(P.E.voices, P.E.voices ? P.E.ctl[CTL_STREAM] : 0, token, P.E.dim);
     for (int i = tid; i < P.E.dim; i += blockDim.x) {
         float v = embed_value(P.E.table, P.E.wtype, P.E.dim, token, i);
-        if (gr >= 0) v += P.E.gamma_val[(long long)gr * P.E.dim + i];
+        if (gam) v += gam[i];
         P.E.x[i] = v;
     }
 }

@@ -108,6 +108,8 @@ struct PdParams {
     const unsigned short *lmsimg;    // [256][5][512]
     const float *norms;              // [L][2][D] attn_norm | ffn_norm of every layer, then [D] output_norm (packed by pd_build)
     const uint8_t *embd_raw;         // Q8_0 rows of token_embd (a Q4_0 / Q5_0 file: its values re-blocked as Q8_0 by pd_embd_q8_kernel)
+    const int *gamma_row;            // gamma essence of the stream's voice (go/model.go:503-505): [V] row of gamma_val or -1; nullptr = none
+    const float *gamma_val;          // [n][D]
     const float *rope_cos, *rope_sin;
     float *kcache, *vcache;          // layer 0 of the stream: [kv head][seq][64]
     long long kv_layer_stride;
@@ -514,7 +516,9 @@ __device__ __forceinline__ float pd_rowsum(const float *p, int q) {
     return a;
 }
 
-template <int NB, int NBI, int KVH>   // D / 32, I / 32, kv heads: one instantiation per shape class
+// D / 32, I / 32, kv heads: one instantiation per shape class -- and per GAMMA: the launch of a stream whose voice has a gamma
+// table adds its row to the embedding; the no-gamma launch is the kernel it was, instruction for instruction
+template <int NB, int NBI, int KVH, bool GAMMA>
 __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint4 *lmw = reinterpret_cast<uint4 *>(smem);                                          // [5][2][512]
@@ -740,6 +744,14 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
             // ---- embedding row (go/model.go:389-446) ----
             xa = embed_value(P.embd_raw, WT_Q8_0, D, token, c0);
             xb = embed_value(P.embd_raw, WT_Q8_0, D, token, c1);
+            if (GAMMA) {           // embed[token] += gamma[token] (go/model.go:503-505): in front of the 2^-30 rounding of pd_limbs
+                const int gr = P.gamma_row[token];
+                if (gr >= 0) {
+                    const float *grow = P.gamma_val + (long long)gr * D;
+                    xa += grow[c0];
+                    xb += grow[c1];
+                }
+            }
         } else {
             PD_ACK_HOST_ROWS();
             if (step == P.n_steps) break;

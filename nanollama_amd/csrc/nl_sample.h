@@ -98,10 +98,10 @@ __device__ __forceinline__ void samp_embed_tail(const SampleParams &P, int token
     if (!P.embed) return;
     const EmbedParams &E = P.emb;
     if (E.epoch && threadIdx.x == 0) *E.epoch = *E.epoch + 1;            // the forward counter, as embed_kernel advances it
-    const int gr = E.gamma_row ? E.gamma_row[token] : -1;
+    const float *gam = voice_gamma(E.voices, E.voices ? E.ctl[CTL_STREAM] : 0, token, E.dim);
     for (int i = threadIdx.x; i < E.dim; i += blockDim.x) {
         float v = embed_value(E.table, E.wtype, E.dim, token, i);
-        if (gr >= 0) v += E.gamma_val[(long long)gr * E.dim + i];
+        if (gam) v += gam[i];
         E.x[i] = v;
     }
 }

@@ -59,6 +59,7 @@ class LlamaModel:
         self.config = config
         self.state = LlamaState(config.vocab_size)
         self.gamma = None  # go/model.go:23 (gamma injection is out of scope)
+        self.voices = {}   # name -> voice id (1 .. 63) of the gamma essences defined with set_voice; voice 0 is `gamma`
         self._h = handle
         self.max_streams = max_streams
 
@@ -218,6 +219,30 @@ class LlamaModel:
         _lib.check(self._h, _lib.lib().nl_set_gamma(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size),
                                                     vals.ctypes.data, int(vals.dtype == np.float16)))
         self.gamma = (idx, vals) if idx.size else None
+
+    def set_voice(self, voice: int, indices, values) -> None:
+        """nl_set_voice: voice 0 is set_gamma; voices 1 .. 63 are further gamma essences with set_gamma's arguments and rules
+        (an empty index list removes the voice).  `voices` (name -> id) is the caller's to keep."""
+        if int(voice) == 0:
+            return self.set_gamma(indices, values)
+        idx = np.ascontiguousarray(indices, dtype=np.int32)
+        vals = np.ascontiguousarray(values)
+        if vals.dtype not in (np.float32, np.float16):
+            vals = vals.astype(np.float32)
+        if idx.size and (vals.ndim != 2 or vals.shape != (idx.size, self.config.embed_dim)):
+            raise ValueError(f"gamma embed_dim {vals.shape} != model dim {self.config.embed_dim}")  # go/main.go:75-77
+        _lib.check(self._h, _lib.lib().nl_set_voice(self._h, int(voice), idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size),
+                                                    vals.ctypes.data, int(vals.dtype == np.float16)))
+
+    def stream_voice(self, stream: int, voice: int) -> None:
+        """nl_stream_voice: the tokens `stream` embeds from now on take `voice`'s gamma (0: the default voice)."""
+        _lib.check(self._h, _lib.lib().nl_stream_voice(self._h, int(stream), int(voice)))
+
+    def voice_info(self, stream: int = 0):
+        """nl_voice_info: the voice `stream` is bound to and how many voices (0 included) hold a table."""
+        v, n = C.c_int(0), C.c_int(0)
+        _lib.check(self._h, _lib.lib().nl_voice_info(self._h, int(stream), C.byref(v), C.byref(n)))
+        return {"voice": v.value, "defined": n.value}
 
     # --- Reset go/model.go:623 ---
     def reset(self, stream: int = 0) -> None:

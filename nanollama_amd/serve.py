@@ -4,7 +4,10 @@
     POST /chat    {"messages":[{"role","content"}], "temperature", "max_tokens", "top_k"} -> {"response"}
     POST /score   {"text"} or {"prompt","continuation"} (+ "details": true) -> {"tokens","logprob","nll","ppl","bpb"}
                   (+ "token_logprobs"); no counterpart in go/serve.go -- the quantity is nanollama/core_eval.py's bits per byte
+                  Both bodies take an optional "voice": NAME (one of the server's --voice names; absent: the default voice,
+                  --gamma or none); an unknown name is 400 {"error"}
     GET  /health  {"status","params_millions","layers","dim","heads","kv_heads","vocab_size","gamma_loaded"}
+                  (+ "voices": [names] when the server has --voice entries)
                   (+ "steps","prefill_chunk","max_step_gap_ms" with --parallel N)
 
 One generation at a time (the model handle is single-caller): a lock around GenerateQuiet, as go/serve.go:56,106-108.
@@ -36,6 +39,29 @@ document.getElementById('msg').addEventListener('keydown',e=>{if(e.key==='Enter'
 </script></body></html>"""
 
 
+def _voices(engine) -> dict:
+    return getattr(getattr(engine, "model", None), "voices", None) or {}
+
+
+def request_voice(engine, req: dict) -> int:
+    """The voice id a request body asks for: "voice": NAME among the model's voices; absent: 0, the default voice.
+    Raises RequestError (400, JSON) for anything else."""
+    name = req.get("voice")
+    if name is None:
+        return 0
+    voices = _voices(engine)
+    if not isinstance(name, str) or name not in voices:
+        raise RequestError(400, f"unknown voice {name!r}: this server has {sorted(voices) if voices else 'no named voices'}")
+    return voices[name]
+
+
+def bind_voice(engine, voice: int) -> None:
+    """One-caller engine: stream 0 speaks as `voice` from here on (called under the request lock).  A model without named
+    voices has every stream on voice 0 for good."""
+    if _voices(engine):
+        engine.model.stream_voice(0, voice)
+
+
 def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
     """POST /chat (go/serve.go:69-111).  Returns (status, payload)."""
     try:
@@ -44,6 +70,10 @@ def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
             raise ValueError("request must be a JSON object")
     except (ValueError, UnicodeDecodeError) as exc:
         return 400, "bad request: " + str(exc)
+    try:
+        voice = request_voice(engine, req)
+    except RequestError as exc:
+        return exc.status, {"error": str(exc)}
     messages = req.get("messages") or []
     if len(messages) == 0:
         return 200, {"response": "Send a message."}
@@ -60,7 +90,11 @@ def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
         params = replace(params, top_k=int(req["top_k"]))
     try:
         with lock:
-            result = engine.generate_quiet(prompt, params)
+            if isinstance(engine, BatchScheduler):
+                result = engine.generate_quiet(prompt, params, voice=voice)
+            else:
+                bind_voice(engine, voice)
+                result = engine.generate_quiet(prompt, params)
     except RequestError as exc:             # (batch scheduler: settings it cannot serve, or an engine error)
         return exc.status, str(exc)
     return 200, {"response": result}
@@ -84,13 +118,19 @@ def handle_score(engine, lock, body: bytes):
             raise ValueError("nothing to score: empty " + ("text" if text is not None else "continuation"))
     except (ValueError, UnicodeDecodeError) as exc:
         return 400, "bad request: " + str(exc)
+    try:
+        voice = request_voice(engine, req)
+    except RequestError as exc:
+        return exc.status, {"error": str(exc)}
     # a BatchScheduler scores on a stream of its own worker (its score(ids, n_context)); a TextEngine's handle is single-caller
     if isinstance(engine, BatchScheduler):
-        run = lambda model, ids, stream, n_context: engine.score(ids, n_context)
+        run = lambda model, ids, stream, n_context: engine.score(ids, n_context, voice=voice)
     else:
         from .score import score_ids as run
     try:
         with lock:
+            if not isinstance(engine, BatchScheduler):
+                bind_voice(engine, voice)
             if text is not None:
                 r = score_text(engine.model, engine.tokenizer, text, score=run)
             else:
@@ -113,6 +153,8 @@ def handle_health(engine):
     out = {"status": "ok", "params_millions": estimate_params(c) // 1_000_000, "layers": c.num_layers,
            "dim": c.embed_dim, "heads": c.num_heads, "kv_heads": c.num_kv_heads, "vocab_size": c.vocab_size,
            "gamma_loaded": engine.model.gamma is not None}
+    if _voices(engine):                          # a server with --voice entries: their names (none: the reference's keys, no more)
+        out["voices"] = list(_voices(engine))
     if isinstance(engine, BatchScheduler):       # --parallel N: the scheduler's counters (tools/bench_serve_parallel.py)
         out.update(steps=engine.steps, prefill_chunk=engine.prefill_chunk, max_step_gap_ms=round(engine.max_step_gap_ms, 3))
     return out

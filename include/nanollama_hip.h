@@ -276,6 +276,8 @@ NL_API int nl_op_exp(int device, const float *x, float *out, int n);
  * blocks store `iters` generations each, n reader blocks on other XCDs count every copy they read (*seen) and every copy whose
  * four words are not of one generation (*torn; the engine assumes 0). */
 NL_API int nl_op_gran16_soak(int device, int n, unsigned iters, unsigned long long *torn, unsigned long long *seen);
+/* the same property for the in-XCD form of the persistent decode's h hand-off: `pairs` (1 .. 16) writer / reader pairs on each XCD */
+NL_API int nl_op_gran16_soak_local(int device, int pairs, unsigned iters, unsigned long long *torn, unsigned long long *seen);
 
 /* Sampling operator on host logits: one decision of sampleTopP / sampleTopK / argmax (go/main.go:294-408)
  * after the in-place repetition penalty (:177-187), on the device.  logits (in/out: the penalty is applied in

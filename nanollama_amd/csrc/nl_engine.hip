@@ -471,7 +471,8 @@ struct nl_engine {
         uint8_t *embd_q8 = nullptr;  // token_embd of a Q4_0 / Q5_0 file re-blocked as Q8_0 for the in-launch lookup
         uint4 *wimg = nullptr, *lmimg = nullptr;
         unsigned short *simg = nullptr, *lmsimg = nullptr;
-        pd_u64 *gx = nullptr, *gqkv = nullptr, *go = nullptr, *gxp = nullptr, *gh = nullptr;
+        pd_u64 *gx = nullptr, *gqkv = nullptr, *go = nullptr, *gxp = nullptr;
+        pd_u32x4 *gh = nullptr;          // h: 16-byte granules (pd_h_row)
         pd_u64 *gpart = nullptr;
         pd_u32x4 *gam = nullptr;
         unsigned *census = nullptr, *status = nullptr, *h_status = nullptr;
@@ -1545,12 +1546,13 @@ int pd_build(nl_engine *e) {
     HIPCK(e, dalloc(&d.gqkv, L1 * 3 * c.dim, &e->bytes_state));
     HIPCK(e, hipMemset(d.gqkv, 0, L1 * 3 * c.dim * 8));
     HIPCK(e, dalloc(&d.gxp, L1 * c.dim, &e->bytes_state));
-    HIPCK(e, dalloc(&d.gh, L1 * c.interm, &e->bytes_state));
+    const size_t hgran = L1 * (size_t)(c.interm / pd_h_vpg(c.interm));       // (L + 1) * S granules of 16 bytes
+    HIPCK(e, dalloc(&d.gh, hgran, &e->bytes_state));
     HIPCK(e, dalloc(&d.gam, (size_t)PD_GRID, &e->bytes_state));
     HIPCK(e, dalloc(&d.gpart, (size_t)c.n_layers * c.n_heads * (PD_PARTS - 1) * 66, &e->bytes_state));
     HIPCK(e, hipMemset(d.gpart, 0, (size_t)c.n_layers * c.n_heads * (PD_PARTS - 1) * 66 * 8));
     HIPCK(e, hipMemset(d.gx, 0, L1 * c.dim * 8)); HIPCK(e, hipMemset(d.go, 0, L1 * c.dim * 8)); HIPCK(e, hipMemset(d.gxp, 0, L1 * c.dim * 8));
-    HIPCK(e, hipMemset(d.gh, 0, L1 * c.interm * 8)); HIPCK(e, hipMemset(d.gam, 0, (size_t)PD_GRID * 16));
+    HIPCK(e, hipMemset(d.gh, 0, hgran * 16)); HIPCK(e, hipMemset(d.gam, 0, (size_t)PD_GRID * 16));
     HIPCK(e, dalloc(&d.norms, ((size_t)c.n_layers * 2 + 1) * c.dim, &e->bytes_state));
     for (int l = 0; l < c.n_layers; l++) {
         HIPCK(e, hipMemcpy(d.norms + (size_t)(2 * l) * c.dim, e->layers[l].attn_norm, (size_t)c.dim * 4, hipMemcpyDeviceToDevice));
@@ -1601,7 +1603,7 @@ int pd_launch(nl_engine *e, int stream, int token, int pos, int n, float *host_l
         const size_t L1 = (size_t)c.n_layers + 1;
         HIPCK(e, hipMemsetAsync(d.gx, 0, L1 * c.dim * 8, e->stream)); HIPCK(e, hipMemsetAsync(d.go, 0, L1 * c.dim * 8, e->stream));
         HIPCK(e, hipMemsetAsync(d.gqkv, 0, L1 * 3 * c.dim * 8, e->stream));
-        HIPCK(e, hipMemsetAsync(d.gxp, 0, L1 * c.dim * 8, e->stream)); HIPCK(e, hipMemsetAsync(d.gh, 0, L1 * c.interm * 8, e->stream));
+        HIPCK(e, hipMemsetAsync(d.gxp, 0, L1 * c.dim * 8, e->stream)); HIPCK(e, hipMemsetAsync(d.gh, 0, L1 * (size_t)(c.interm / pd_h_vpg(c.interm)) * 16, e->stream));
         HIPCK(e, hipMemsetAsync(d.gam, 0, (size_t)PD_GRID * 16, e->stream));
         HIPCK(e, hipMemsetAsync(d.gpart, 0, (size_t)c.n_layers * c.n_heads * (PD_PARTS - 1) * 66 * 8, e->stream));
         d.tag_base = 0;
@@ -4902,6 +4904,31 @@ int nl_op_gran16_soak(int device, int n, unsigned iters, unsigned long long *tor
         if (hipMalloc((void **)&slots, (size_t)n * 256 * sizeof(u32x4)) != hipSuccess || hipMalloc((void **)&cnt, 16) != hipSuccess) break;
         if (hipMemset(slots, 0, (size_t)n * 256 * sizeof(u32x4)) != hipSuccess || hipMemset(cnt, 0, 16) != hipSuccess) break;
         hipLaunchKernelGGL(gran16_soak_kernel, dim3(2 * n), dim3(256), 0, 0, slots, n, iters, cnt, cnt + 1);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+        unsigned long long h[2];
+        if (hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) break;
+        *torn = h[0]; *seen = h[1];
+        rc = NL_OK;
+    } while (0);
+    if (slots) hipFree(slots);
+    if (cnt) hipFree(cnt);
+    return rc;
+}
+
+// Soak of the in-XCD 16-byte granule form of the persistent decode's h hand-off (nl_persist.h pd_gran16_soak_local_kernel): 256
+// blocks, `pairs` writer / reader pairs per XCD as placement turns out (the rest leave at once).
+int nl_op_gran16_soak_local(int device, int pairs, unsigned iters, unsigned long long *torn, unsigned long long *seen) {
+    if (!torn || !seen || pairs < 1 || pairs > PD_CUS / 2 || iters < 1 || iters > (1u << 24)) return NL_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
+    pd_u32x4 *slots = nullptr;
+    unsigned long long *cnt = nullptr;      // [0] torn, [1] seen, then the XCDs' ticket words
+    const size_t nslot = (size_t)PD_XCDS * pairs * 256;
+    int rc = NL_ERR_HIP;
+    do {
+        if (hipMalloc((void **)&slots, nslot * sizeof(pd_u32x4)) != hipSuccess || hipMalloc((void **)&cnt, 64) != hipSuccess) break;
+        if (hipMemset(slots, 0, nslot * sizeof(pd_u32x4)) != hipSuccess || hipMemset(cnt, 0, 64) != hipSuccess) break;
+        hipLaunchKernelGGL(pd_gran16_soak_local_kernel, dim3(PD_GRID), dim3(256), 0, 0, slots, reinterpret_cast<unsigned *>(cnt + 2), pairs, iters,
+                           iters * 64u + 1000000u, cnt, cnt + 1);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
         unsigned long long h[2];
         if (hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) break;

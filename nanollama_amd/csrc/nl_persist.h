@@ -30,7 +30,11 @@
 // 2^-30-rounded inputs (pd_limbs / pd_units_impl below).
 // Hand-offs are 8-byte {tag, value} granules (tag = launch base + step + 1; one aligned store each, the value is its own
 // arrival flag), polled with L1-bypassing loads; every poll is bounded and a give-up sets the status word the host checks
-// (it then redoes the chunk on the launch plans and retires this path, like the fused plans of nl_block.h).
+// (it then redoes the chunk on the launch plans and retires this path, like the fused plans of nl_block.h).  h -- which feeds
+// only the digit images, no sum tied to a lane layout -- travels three (I 1536) or two (I 512) values to a 16-byte granule
+// (pd_h_row, pd_publish16 / pd_gather16): a third fewer bytes and one load instead of three per lane and poll.
+// Below position 128 a head's single attention record is normalised and published by the wavefront that reduced it (no record in
+// LDS, no barrier, no merge); a chunk's logits go to device memory only on the launch's last step (every step in a session).
 //
 // RESIDENT SESSION (per-call Forward).  go/main.go:173-219 calls Forward once per token and samples on the host, so the
 // reference's own loop cannot use a chunked launch.  PdParams::session keeps the launch on the chip between nl_forward calls
@@ -76,9 +80,17 @@ __host__ __device__ inline int pd_pad4(int n) { return (n + 3) & ~3; }
 // Unit u of a phase = lane (u & 3) of a group of four lanes that share one 32-column block: rows 4 * (G / NB) + (u & 3) of this
 // compute unit's (padded) rows, block G % NB, G = u / 4 -- one v_mfma_i32_4x4x4_16b_i8 is sixteen such groups
 __host__ __device__ inline void pd_unit_rc(int u, int NB, int &row, int &blk) { const int G = u >> 2; row = (G / NB) * 4 + (u & 3); blk = G % NB; }
+// h = SiLU(gate) * up travels in 16-byte granules {tag, h[g], h[g + S], h[g + 2 S]}, S = I / VPG granules, VPG values each (3 where
+// I % 96 == 0, else 2 where I % 64 == 0, else 0: no such form).  h feeds pd_limbs only -- a maximum per 32-element block and
+// digits per element, no sum -- so which lane holds which element changes no bit; a consumer lane g holds element g + k S of block
+// (g >> 5) + k S / 32: a half wavefront holds one whole block per k.  The rows follow the granules: unit idx owns VPG runs of
+// S / 32 rows, its local gate / up row lr (< I / 32) is h row (lr / (S / 32)) * S + idx * (S / 32) + lr % (S / 32)
+__host__ __device__ constexpr int pd_h_vpg(int I) { return I % 96 == 0 ? 3 : I % 64 == 0 ? 2 : 0; }
+__host__ __device__ inline int pd_h_row(int idx, int lr, int I) { const int S = I / pd_h_vpg(I), SU = S / PD_CUS; return (lr / SU) * S + idx * SU + lr % SU; }
 
 inline bool pd_shape_ok(int D, int I, int H, int KV, int hd, int V, int L) {
     if (hd != 64 || KV < 1 || H % KV || D != H * 64 || D % 32 || I % 32 || H < 1 || H > 16 || L < 1 || L > PD_MAXL) return false;
+    if (!pd_h_vpg(I)) return false;                                              // h's granules: three or two values each
     // the instantiations of pd_decode_kernel: nano's shape with 9 (MHA) or 3 kv heads; a small test shape with 4 or 2
     if (!((D == 576 && I == 1536 && (KV == 9 || KV == 3)) || (D == 256 && I == 512 && (KV == 4 || KV == 2)))) return false;
     const int RQ = D + 2 * KV * 64;                                              // rows of [Q; K; V]
@@ -116,7 +128,7 @@ struct PdParams {
     pd_u64 *gx;                      // [L + 1][D]: input x of layer l >= 1; [L] = the final residual stream
     pd_u64 *gqkv;                    // [L][3 D]: q | k | v rows of the position before RoPE (row-split over the XCD's units, read by the heads)
     pd_u64 *go, *gxp;                // [L][D]: heads' attention outputs; x' = x + WO o
-    pd_u64 *gh;                      // [L][I]: SiLU(gate) * up
+    pd_u32x4 *gh;                    // [L][I / VPG] x 16 B: SiLU(gate) * up, {tag, h[g], h[g + S], h[g + 2 S]} (pd_h_row)
     pd_u64 *gpart;                   // [L][H][PD_PARTS - 1][66]: a helper's merged (max, sum, sum p v[64]) of its passes, for the head's owner
     pd_u32x4 *gam;                   // [256] {tag, max bits, index, -}
     unsigned *census, *census_next;  // [8] tickets per XCD, [8] arrivals of THIS launch; the next launch's words (zeroed here: no memset between launches)
@@ -178,7 +190,7 @@ __global__ void __launch_bounds__(PD_THREADS) pd_pack_kernel(PdPackParams P) {
                 if (u < 2 * grp * NB) {            // rows [0, grp): gate, [grp, 2 grp): up -- padding rows stay zero
                     const bool up = row >= grp;
                     const int rr = up ? row - grp : row;
-                    if (rr < gr) { bt = P.rtype[layer][up ? 5 : 4]; src = P.raw[layer][up ? 5 : 4] + ((size_t)(idx * gr + rr) * NB + blk) * bsz(bt); }
+                    if (rr < gr) { bt = P.rtype[layer][up ? 5 : 4]; src = P.raw[layer][up ? 5 : 4] + ((size_t)pd_h_row(idx, rr, P.I) * NB + blk) * bsz(bt); }
                 }
             } else {
                 const int u = (k - PD_UQ - PD_UW - PD_UG) * PD_THREADS + tid;
@@ -259,6 +271,9 @@ __device__ __forceinline__ pd_u64 pd_ld8(__amdgpu_buffer_rsrc_t r, unsigned byte
     const pd_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, 0, 16);
     return ((pd_u64)v.y << 32) | v.x;
 }
+__device__ __forceinline__ pd_u32x4 pd_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
+    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 16);
+}
 __device__ __forceinline__ float4 pd_ld16f(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
     const pd_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 16);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
@@ -300,9 +315,71 @@ __device__ __forceinline__ void pd_gather(const pd_u64 *g, int n, unsigned tag, 
             break;
         }
         // (no s_sleep between polls: they are this XCD's own L2 round trips, nobody streams beside them -- 7920 -> 8040 tok/s)
+        // (nor for the units without an attention role while the heads work: s_sleep 1 / 2 / 4 in their wait for o moved the token by
+        //  -0.2 / -0.1 / +0.4 us of 121.2, inside the 0.24 us spread of the repeats: EXPERIMENTS)
     }
 #pragma unroll
     for (int k = 0; k < NPT; k++) v[k] = __uint_as_float((unsigned)q[k]);
+}
+
+// h: n 16-byte granules {tag, v0, v1, v2} -> v[k] of granule tid, one load per lane and poll (the form of the argmax exchange).  The
+// producer's one 16-byte store is seen whole or not at all (nl_op_gran16_soak_local).  The loop, its bound and its give-up are pd_gather's.
+constexpr int PD_ST16_AUX = 1;      // sc0: what the workgroup-scope store of pd_publish<false> compiles to (written through the L1 into this XCD's L2)
+constexpr int DPP_ROW_SHL4 = 0x104, DPP_ROW_SHL8 = 0x108;      // row_shl:n -- lane l of a row of 16 reads lane l + n (0 beyond the row)
+__device__ __forceinline__ void pd_publish16(pd_u32x4 *base, unsigned bytes, unsigned idx, unsigned tag, float v0, float v1, float v2) {
+    const pd_u32x4 g = {tag, __float_as_uint(v0), __float_as_uint(v1), __float_as_uint(v2)};
+    __builtin_amdgcn_raw_buffer_store_b128(g, pd_rsrc(base, bytes), (int)(idx * 16u), 0, PD_ST16_AUX);
+}
+__device__ __forceinline__ void pd_gather16(const pd_u32x4 *g, int n, unsigned tag, float (&v)[3], const PdPoll &Q, unsigned code, int tid) {
+    const __amdgpu_buffer_rsrc_t r = pd_rsrc(g, (unsigned)n * 16u);
+    const unsigned off = (unsigned)min(tid, n - 1) * 16u;
+    pd_u32x4 q;
+    for (int spins = 0;; spins++) {
+        q = pd_ld16(r, off);
+        if (__all(q.x == tag)) break;
+        if (spins >= Q.spin_limit || ((spins & 63) == 63 && __hip_atomic_load(Q.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+            pd_give_up(Q, code, tid);
+            break;
+        }
+        // (no s_sleep: see pd_gather)
+    }
+    v[0] = __uint_as_float(q.y); v[1] = __uint_as_float(q.z); v[2] = __uint_as_float(q.w);
+}
+
+// Soak of the property h's granules rest on (nl_op_gran16_soak_local): pd_publish16's one 16-byte in-XCD store is seen whole or not
+// at all by pd_gather16's 16-byte L1-bypassing load of another compute unit of the SAME XCD.  Every block reads XCC_ID and takes a
+// ticket of its XCD (placement observed, as the decode kernel does): tickets 2 p and 2 p + 1 are pair p of the XCD -- the even one
+// writes generations 1 .. iters of a granule whose payload words are functions of its tag, the odd one reads it and counts every
+// copy whose words disagree.  Both loops are bounded: a reader whose writer never came leaves after max_spins loads.
+__global__ void __launch_bounds__(256) pd_gran16_soak_local_kernel(pd_u32x4 *slots, unsigned *tickets, int pairs, unsigned iters, unsigned max_spins,
+                                                                   unsigned long long *torn, unsigned long long *seen) {
+    __shared__ unsigned tk;
+    unsigned xcd;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcd));
+    xcd &= 7u;
+    if (threadIdx.x == 0) tk = atomicAdd(tickets + xcd, 1u);
+    __syncthreads();
+    const unsigned t = tk, pair = t >> 1;
+    if (pair >= (unsigned)pairs) return;
+    const unsigned bytes = (unsigned)(PD_XCDS * pairs * 256) * 16u, slot = (xcd * (unsigned)pairs + pair) * 256u + threadIdx.x;
+    if (!(t & 1u)) {
+        for (unsigned g = 1; g <= iters; g++) {
+            pd_publish16(slots, bytes, slot, g, __uint_as_float(g * 2654435761u + 1u), __uint_as_float(g ^ 0x5bd1e995u), __uint_as_float(~g));
+            if ((g & 7u) == 0u) __builtin_amdgcn_s_sleep(1);
+        }
+        return;
+    }
+    const __amdgpu_buffer_rsrc_t r = pd_rsrc(slots, bytes);
+    unsigned long long bad = 0, reads = 0;
+    for (unsigned spins = 0; spins < max_spins; spins++) {
+        asm volatile("" ::: "memory");      // (every round loads again: nothing in this loop writes memory, the load would be hoisted)
+        const pd_u32x4 v = pd_ld16(r, slot * 16u);
+        reads++;
+        if (v.x != 0u && (v.y != v.x * 2654435761u + 1u || v.z != (v.x ^ 0x5bd1e995u) || v.w != ~v.x)) bad++;
+        if (v.x == iters) break;
+    }
+    atomicAdd(torn, bad);
+    atomicAdd(seen, reads);
 }
 
 // U unit slots of a phase: unit u = k * 512 + tid = (row u / NB, block u % NB) of this compute unit's rows; the lane's
@@ -543,6 +620,8 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
 
     const int tid0 = threadIdx.x;
     constexpr int D = NB * 32, I = NBI * 32, H = D / 64, NBP = NB | 1, NBIP = NBI | 1;
+    constexpr int HVPG = pd_h_vpg(I), HS = I / HVPG, HSU = HS / PD_CUS;      // h's granules: values each, how many, per unit (pd_h_row)
+    static_assert(HVPG >= 2 && HS % 64 == 0 && HS <= PD_THREADS && HSU * HVPG * PD_CUS == I && HSU <= 4 * PD_WAVES, "h granule form");
     constexpr int KVD = KVH * 64, GQ = H / KVH;          // GQA (go/model.go:557-587): query head h reads kv head h / GQ
     static_assert(H % KVH == 0, "query heads per kv head");
     constexpr int QR = (D + 2 * KVD) / PD_CUS, QRP = (QR + 3) & ~3, WR = D / PD_CUS, WRP = (WR + 3) & ~3, GR = I / PD_CUS, GRP = (GR + 3) & ~3;   // this unit's rows per matrix
@@ -778,6 +857,7 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 hidx = j - (apart - 1) * H;
             }
             const bool arole = head || apart < nparts;          // (a helper beyond the passes there are has nothing to do)
+            const bool single = nparts == 1;                    // positions below 128: one pass, one record, no helpers -- heads only
             const int chf = nch - 1 - apart;                    // this unit's first (= highest) pass
             float *const kc = P.kcache + (long long)layer * P.kv_layer_stride + (long long)(arole ? hidx / GQ : 0) * P.seq_len * 64;
             float *const vc = P.vcache + (long long)layer * P.kv_layer_stride + (long long)(arole ? hidx / GQ : 0) * P.seq_len * 64;
@@ -909,8 +989,14 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                             float ov = 0.f;
 #pragma unroll
                             for (int w = 0; w < 8; w++) ov = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wgt), w)), wpart[w * 68 + 4 + lane], ov);
-                            chunk[nci * 66 + 2 + lane] = ov;
-                            if (lane == 0) { chunk[nci * 66] = M; chunk[nci * 66 + 1] = Ls; }
+                            if (single) {      // the only record there is: o leaves from here -- no record in LDS, no barrier, no merge below
+                                if (s == 0 && idx == 0) PD_ST(sb, 5);
+                                pd_publish<false>(P.go + (size_t)layer * D + hidx * 64 + lane, tag, ov * (1.0f / Ls));
+                                if (s == 0 && idx == 0) PD_ST(sb, 6);
+                            } else {
+                                chunk[nci * 66 + 2 + lane] = ov;
+                                if (lane == 0) { chunk[nci * 66] = M; chunk[nci * 66 + 1] = Ls; }
+                            }
                         }
                         if (ch - PD_PARTS >= 0) __syncthreads();
                     }
@@ -932,11 +1018,12 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                         }
                         nci += np1;
                     }
-                    __syncthreads();
+                    // (single: no poll has run since the check behind the q | k | v gather, and nothing below reads LDS this phase wrote)
+                    if (!single) __syncthreads();
                     PD_RELANE();
-                    if (misc[2]) return;
-                    if (s == 0 && idx == 0) PD_ST(sb, 5);
-                    if (tid < 64) {
+                    if (!single && misc[2]) return;
+                    if (!single && s == 0 && idx == 0) PD_ST(sb, 5);
+                    if (!single && tid < 64) {
                         // the records merged like position splits (fixed order: own passes from the highest down, then the helpers by part)
                         float M = chunk[0];
                         for (int c = 1; c < nci; c++) M = fmaxf(M, chunk[c * 66]);
@@ -955,13 +1042,13 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                             if (tid == 0) { pd_publish<false>(dst, tag, M); pd_publish<false>(dst + 1, tag, Ls); }
                         }
                     }
-                    if (s == 0 && idx == 0) PD_ST(sb, 6);
+                    if (!single && s == 0 && idx == 0) PD_ST(sb, 6);
                 }
             }
             {
                 // =============================== every unit: WO, gate / up, down rows ===============================
-                constexpr int nr = WR, nrp = WRP, rg = GR, rgp = GRP;
-                const int r0 = idx * WR, g0 = idx * GR;
+                constexpr int nr = WR, nrp = WRP, rgp = GRP;
+                const int r0 = idx * WR;
                 // ---- o of every head -> LDS; WO rows + residual (go/model.go:590-594) ----
                 {
                     float ov[2];
@@ -1003,25 +1090,31 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 PD_RELANE();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 7);
                 // row sums and SiLU(gate) * up without a round trip through LDS: a quad = the gate row and the up row of one index,
-                // two lanes each
-                if ((tid >> 2) < rg) {
-                    const int row = tid >> 2, mat = (tid >> 1) & 1;
+                // two lanes each.  A row of 16 lanes = one granule (pd_h_row): quads 0 .. VPG - 1 hold its values k = 0 .. VPG - 1 (local
+                // rows k * HSU + i, i = 4 * wave + row of 16), two row shifts bring them to the quad-0 lane, which stores the granule
+                if (wave * 4 < HSU) {          // (wave-uniform: every lane of the wavefront is here for the shifts)
+                    const int i = min(tid >> 4, HSU - 1), k = min((tid >> 2) & 3, HVPG - 1), row = k * HSU + i, mat = (tid >> 1) & 1;
                     const float own = pd_rowsum<NB, 2>(part + (mat * rgp + row) * NBP, tid & 1) * inv2;
                     const float other = dpp_f32<DPP_QUAD_XOR2>(own);
+                    float hval = 0.f;
                     if (!(tid & 3)) {
                         const float g = own, u = other;
                         const float ex = pd_exp(-g);
-                        pd_publish<false>(P.gh + (size_t)layer * I + g0 + row, tag, (g / (1.0f + ex)) * u);
+                        hval = (g / (1.0f + ex)) * u;
                     }
+                    const float h1 = dpp_f32<DPP_ROW_SHL4>(hval), h2 = dpp_f32<DPP_ROW_SHL8>(hval);      // lane l: the value of lane l + 4, l + 8 of its row
+                    if (!(tid & 15) && (tid >> 4) < HSU)
+                        pd_publish16(P.gh + (size_t)layer * HS, (unsigned)HS * 16u, (unsigned)(idx * HSU + (tid >> 4)), tag, hval, h1, HVPG == 3 ? h2 : 0.f);
                 }
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 8);
                 // ---- h of every worker -> LDS; down rows + residual (go/model.go:609-612) ----
                 {
                     float hv[3];
-                    pd_gather<3>(P.gh + (size_t)layer * I, I, tag, hv, Q, 8u, tid);
+                    if (wave * 64 < HS) {      // granule tid: elements tid + k * HS, a whole block per half wavefront and k
+                        pd_gather16(P.gh + (size_t)layer * HS, HS, tag, hv, Q, 8u, tid);
 #pragma unroll
-                    for (int k = 0; k < 3; k++)
-                        if (wave * 64 + k * PD_THREADS < I) pd_limbs(hv[k], tid + k * PD_THREADS < I, tid + k * PD_THREADS, hl, hs, lane);
+                        for (int k = 0; k < HVPG; k++) pd_limbs(hv[k], true, tid + k * HS, hl, hs, lane);
+                    }
                 }
                 __syncthreads();
                 PD_RELANE();
@@ -1072,9 +1165,11 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 const float lg = pd_rowsum<NB, 2>(part + min(row, 127) * NBP, tid & 1) * inv;
                 if (row < lm_n) {
                     if (!(tid & 1)) {
-                        P.logits[lm_r0 + row] = lg;
-                        if (P.host_logits && (P.session || step == P.n_steps - 1))      // per-call Forward: no DMA behind the launch
-                            __hip_atomic_store(P.host_logits + lm_r0 + row, lg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        if (P.session || step == P.n_steps - 1) {      // a chunk's earlier logits are read by nobody: a session's step and the launch's last one are
+                            P.logits[lm_r0 + row] = lg;
+                            if (P.host_logits)                          // per-call Forward: no DMA behind the launch
+                                __hip_atomic_store(P.host_logits + lm_r0 + row, lg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        }
                     }
                     if (lg > best) { best = lg; bidx = lm_r0 + row; }
                 }

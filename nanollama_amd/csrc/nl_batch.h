@@ -1103,8 +1103,12 @@ __global__ void __launch_bounds__(QT * G * 4, QT * G >= 128 ? 4 : 2) attn_tile16
         //      The vector pipe is this kernel's busiest (SQ_INSTS_VALU x 4 cycles ~ 40 % of the launch, all of it on the
         //      critical path of the longest runs), so everything is kept in the log2 domain and two elements per
         //      instruction (v_pk_mul_f32 / v_pk_add_f32): t = s * (scale * log2 e); p * 2^10 = exp2(t + (10 - max)) on
-        //      v_exp_f32 (~1 ulp; the two roundings of the argument add < 1.5e-6 relative for |t| < 32); max and sum
-        //      leave in natural units (max * ln 2, sum * 2^-10) ----
+        //      v_exp_f32 (~1 ulp).  The two roundings of the argument (s * c2, then + nb) are half an ulp of |t| each, together
+        //      <= ulp(|t|) * ln 2 relative on p: 1.3e-6 for |t| < 32, 1.1e-5 at |t| ~ 170 (a key 120 nats up) -- what the
+        //      float32 rounding of the score itself costs on every path.  The row's maximum has the argument 10 to within the
+        //      rounding of nb = 10 - max (half an ulp of |max| + 10 at most: the same order again).  No range of t is
+        //      assumed: tests/test_gpu_attention_sharp.py holds prompts to float64 with |t| up to 180 (DESIGN section 5 has
+        //      the measured values); max and sum leave in natural units (max * ln 2, sum * 2^-10) ----
         //      (two separate instruction streams: with the masked variant merely branched around, hipcc hoists its 32
         //      compares into the common path)
         float alpha;

@@ -142,6 +142,9 @@ class F64Run:
     top2_gap: np.ndarray    # [T, layer, head]: best minus second best score (inf at position 0)
     over_median: np.ndarray # [T, layer, head]: best minus the median score of the row
     split_gap: np.ndarray   # [T, layer, head, splits]: m_c - M per SPLIT-key split, nan where the split holds no key yet
+    norm_ms: Optional[np.ndarray] = None   # [T, 2 layers + 1]: mean(x^2) of every RMSNorm's input (attention, feed-forward, ..., final)
+    gate: Optional[np.ndarray] = None      # [T, layer, I]: the SiLU's pre-activations
+    chan_ms: Optional[np.ndarray] = None   # [2 layers + 1, D]: mean over the steps of x^2 per channel of every RMSNorm's input
 
 
 class F64Model:
@@ -201,7 +204,14 @@ class F64Model:
         top2, sgap = np.full((T, L, H), np.inf), np.full((T, L, H, nsplit), np.nan)
         overmed = np.zeros((T, L, H))
         causal = pos[None, :] <= pos[:, None]
+        norm_ms, chan_ms, gates = [], [], []
+
+        def norm_in(x):                   # the input of an RMSNorm
+            norm_ms.append((x * x).mean(axis=-1))
+            chan_ms.append((x * x).mean(axis=0))
+
         for l, W in enumerate(self.layers):
+            norm_in(x)
             xb = self._rms(x, W["attn_norm"])
             q, k, v = xb @ W["wq"].T, xb @ W["wk"].T, xb @ W["wv"].T
             if W["bq"] is not None: q = q + W["bq"]
@@ -228,11 +238,16 @@ class F64Model:
             o = att.reshape(T, H * hd) @ W["wo"].T
             if W["bo"] is not None: o = o + W["bo"]
             x = x + o
+            norm_in(x)
             xb = self._rms(x, W["ffn_norm"])
             g_, u = xb @ W["gate"].T, xb @ W["up"].T
-            x = x + ((g_ / (1.0 + np.exp(-g_))) * u) @ W["down"].T
+            gates.append(g_)
+            with np.errstate(over="ignore"):       # exp(-g) = inf for g < -709: g / inf = -0, the limit
+                x = x + ((g_ / (1.0 + np.exp(-g_))) * u) @ W["down"].T
+        norm_in(x)
         logits = self._rms(x, self.out_norm) @ self.out.T
-        return F64Run(logits, ks, vs, amax, mx, top2, overmed, sgap)
+        return F64Run(logits, ks, vs, amax, mx, top2, overmed, sgap,
+                      np.stack(norm_ms, axis=1), np.stack(gates, axis=1), np.stack(chan_ms, axis=0))
 
 
 def forward_f64(g: gguf.GGUFFile, toks) -> F64Run:

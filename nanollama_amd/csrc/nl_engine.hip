@@ -166,6 +166,15 @@ struct StepKnobs {
     int x1_gemm() const { return prefill == Precision::fp16x1 || prefill == Precision::fp16x1_gemm; }
     int x1_attn() const { return prefill == Precision::fp16x1 || prefill == Precision::fp16x1_attn; }
 };
+// Everything that shapes a launch of a captured step (run_step_graph): rows, output rows, rows on the per-token attention kernel,
+// entries of the segment work list, position splits of the per-token rows, a sampler behind the step, the step knobs.  A decode
+// step of m rows is {m, m, m, 0, splits over all its rows}; a mixed step's splits are those of its first n_tok rows.
+struct StepKey {
+    int n, n_out, n_tok, n_work, nsplit;
+    bool sampled;
+    StepKnobs knobs;
+    bool operator==(const StepKey &) const = default;
+};
 #pragma clang diagnostic pop
 
 thread_local std::string g_create_error;
@@ -363,8 +372,8 @@ struct nl_engine {
     // Concurrent sub-batches of a decode batch (nl_forward_batch): the streams of a batch are independent (go/serve.go:106-108
     // serialises them only because it has one CPU engine), so the batch is cut into groups that step on their own HIP stream
     // with their own step buffers -- one dependent chain's launch heads and memory round trips overlap another's work.
-    // Each group's step is a hipGraph cached by (tokens, position splits, step knobs): twice the launches would otherwise bind on the host.
-    struct StepGraph { int m; int nsplit; StepKnobs knobs; hipGraph_t graph; hipGraphExec_t exec; };
+    // Each group's step is a hipGraph cached by its StepKey: twice the launches would otherwise bind on the host.
+    struct StepGraph { StepKey key; hipGraph_t graph; hipGraphExec_t exec; };
     struct SubBatch {
         Batch bt;
         hipStream_t st = nullptr;
@@ -373,17 +382,16 @@ struct nl_engine {
     } sub[4];
     int dg_state = 0;             // dgemm_kernel's weight copies: 0 not looked at yet, 1 built, -1 the model does not qualify
     bool dg_head = false;         // ... and the LM head has one too (decode batches: dgemm_kernel with the argmax candidates in its epilogue)
-    std::vector<StepGraph> bt_graphs;   // step graphs of the whole-batch decode step (bt), same key
+    std::vector<StepGraph> bt_graphs;   // step graphs of the whole-batch decode step (bt)
     hipEvent_t sub_fork = nullptr;
 
     // sampled decode batches (nl_forward_batch_sample): the 64-row sampler's scratch, the call's block (settings | uniforms |
-    // window lengths | ids | windows, bs_layout) in pinned and device memory, and step + sampler graphs keyed like bt_graphs
+    // window lengths | ids | windows, bs_layout) in pinned and device memory, and the step + sampler graphs
     SampScratch bs;
     int *bs_dev = nullptr, *h_bs = nullptr;
     std::vector<StepGraph> bs_graphs;
-    // mixed steps (nl_forward_mixed / nl_forward_mixed_sample): step (+ sampler) graphs keyed on everything that shapes a launch
-    struct MixedGraph { int n, n_out, n_tok, n_work, ns_tok; bool sampled; StepKnobs knobs; hipGraph_t graph; hipGraphExec_t exec; };
-    std::vector<MixedGraph> mx_graphs;
+    // mixed steps (nl_forward_mixed / nl_forward_mixed_sample): step (+ sampler) graphs, at most MX_MAX_GRAPHS of them
+    std::vector<StepGraph> mx_graphs;
 
     // on-device sampling (nl_sample_decode): scratch for one vocabulary, allocated on first use
     SampScratch sp;
@@ -2412,45 +2420,127 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
     return NL_OK;
 }
 
-// One decode-batch step of m streams on stream st: their (token, position, stream) into the pinned block behind b.h_meta, then the
-// step as a hipGraph from `graphs` cached by (m, position splits, step knobs) -- it reads its tokens / positions / streams from that
-// block (a copy node), so one graph serves every step of that geometry.  The 150+ launches of a step are 3 us each when a host
-// thread queues them one by one -- more than the kernels of a decode batch.  A step whose capture fails runs eagerly.
-int decode_step(nl_engine *e, nl_engine::Batch &b, std::vector<nl_engine::StepGraph> &graphs, hipStream_t st, const int *streams,
-                const int *tokens, const int *pos, int m, const StepKnobs &k) {
-    int nsplit = 1;
-    for (int i = 0; i < m; i++) {
-        b.h_meta[i] = tokens[i];
-        b.h_meta[b.cap + i] = pos[i];
-        b.h_meta[2 * b.cap + i] = streams[i];
-        nsplit = std::max(nsplit, pos[i] / ATT_CH + 1);
-    }
+// The step buffers of b and the weight copies a step under knobs k multiplies with, allocated at the first call; `also` runs under
+// the same hold of g_setup_mu (further allocations, or a check against what was allocated).
+template <class F>
+int batch_ready(nl_engine *e, nl_engine::Batch &b, const StepKnobs &k, int cap_limit, F &&also) {
+    std::lock_guard<std::mutex> setup(g_setup_mu);
+    if (int rc = batch_alloc(e, b, cap_limit)) return rc;
+    if (int rc = dgemm_prepare(e, k)) return rc;
+    return also();
+}
+int batch_ready(nl_engine *e, nl_engine::Batch &b, const StepKnobs &k, int cap_limit = 2048) {
+    return batch_ready(e, b, k, cap_limit, [] { return (int)NL_OK; });
+}
+
+// row i of the step b.h_meta describes; returns the attention splits (128-key chunks) a row at this position sees.  The block is
+// reused by every step on b: whoever fills it for a further step synchronises with the step before first.
+int fill_meta(nl_engine::Batch &b, int i, int token, int pos, int stream) {
+    b.h_meta[i] = token;
+    b.h_meta[b.cap + i] = pos;
+    b.h_meta[2 * b.cap + i] = stream;
+    return pos / ATT_CH + 1;
+}
+
+// The step-graph cache: body(st) queues one step on st, which reads its tokens / positions / streams (and whatever else varies
+// from call to call) from pinned blocks by copy nodes, so one hipGraph serves every step of the geometry `key` names.  Launches
+// the graph `graphs` holds for the key; else, with graphs on and fewer than max_graphs of them held, captures body, keeps the
+// graph and launches it; else -- no graphs, a full cache, a capture that failed -- runs body eagerly.  The 150+ launches of a
+// step are 3 us each when a host thread queues them one by one -- more than the kernels of a decode batch.
+template <class Body>
+int run_step_graph(nl_engine *e, std::vector<nl_engine::StepGraph> &graphs, const StepKey &key, hipStream_t st, size_t max_graphs, Body &&body) {
     hipGraphExec_t exec = nullptr;
     for (const auto &G : graphs)
-        if (G.m == m && G.nsplit == nsplit && G.knobs == k) exec = G.exec;
-    if (!exec && e->use_graph) {
+        if (G.key == key) exec = G.exec;
+    if (!exec && e->use_graph && graphs.size() < max_graphs) {
         std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
         hipGraph_t gr = nullptr;
         if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int rc = batched_step(e, b, st, m, 1, k);
+            const int rc = body(st);
             const hipError_t ce = hipStreamEndCapture(st, &gr);
-            if (!rc && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess) graphs.push_back({m, nsplit, k, gr, exec});
+            if (!rc && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess) graphs.push_back({key, gr, exec});
             else { if (gr) (void)hipGraphDestroy(gr); exec = nullptr; }
         }
         (void)hipGetLastError();
     }
-    if (!exec) return batched_step(e, b, st, m, 1, k);
+    if (!exec) return body(st);
     HIPCK(e, hipGraphLaunch(exec, st));
     return NL_OK;
 }
 
-// every cached decode-batch step graph, whole-batch and sub-batch (they hold the device pointers of the step)
+// One decode-batch step of m streams on stream st: their (token, position, stream) into the pinned block behind b.h_meta (outside
+// the captured body), then the step through the cache `graphs`.
+int decode_step(nl_engine *e, nl_engine::Batch &b, std::vector<nl_engine::StepGraph> &graphs, hipStream_t st, const int *streams,
+                const int *tokens, const int *pos, int m, const StepKnobs &k) {
+    int nsplit = 1;
+    for (int i = 0; i < m; i++) nsplit = std::max(nsplit, fill_meta(b, i, tokens[i], pos[i], streams[i]));
+    return run_step_graph(e, graphs, {m, m, m, 0, nsplit, false, k}, st, SIZE_MAX, [&](hipStream_t s2) { return batched_step(e, b, s2, m, 1, k); });
+}
+
+struct StepRow { int token, pos, stream; };
+struct NoHook { int operator()() const { return NL_OK; } int operator()(int) const { return NL_OK; } };
+
+// The single-token row loop of the batched entry points: n steps of the launch plan on e->stream, step j on row(j) (a StepRow, in
+// execution order) with whatever after_row(j) queues behind its launch; `before` runs at the head of every attempt, `tail` behind
+// the last step (the sampled paths: the block up and down), then the synchronise -- and once more from `before` on the general plan when a fused launch timed out
+// (take_fused_timeout: every buffer a step writes is rewritten).  Step j's control block is slot j % ctl_ring_cap of the pinned
+// ring, and the stream is drained before slot 0 is taken again; only a mixed step gets there: every other caller has
+// n <= max(seq_len, max_streams) = ctl_ring_cap.
+template <class Row, class AfterRow, class Before = NoHook, class Tail = NoHook>
+int single_steps(nl_engine *e, int n, Row &&row, AfterRow &&after_row, Before &&before = Before{}, Tail &&tail = Tail{}) {
+    int rc;
+    for (int attempt = 0;; attempt++) {
+        if ((rc = before())) return rc;
+        for (int j = 0; j < n; j++) {
+            const int slot = j % e->ctl_ring_cap;
+            if (j > 0 && slot == 0) HIPCK(e, hipStreamSynchronize(e->stream));
+            const StepRow r = row(j);
+            int *c = e->h_ctl_ring + (size_t)slot * CTL_WORDS;
+            c[CTL_TOKEN] = r.token; c[CTL_POS] = r.pos; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = r.stream;
+            HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
+            if ((rc = launch_step(e, r.pos))) return rc;
+            if ((rc = after_row(j))) return rc;
+        }
+        if ((rc = tail())) return rc;
+        HIPCK(e, hipStreamSynchronize(e->stream));
+        if (attempt == 0 && take_fused_timeout(e)) continue;
+        break;
+    }
+    return NL_OK;
+}
+
+// The multi-token path of a prompt (nl_prefill, nl_score): tiles of e->bt.cap tokens on the matrix cores, causality from each
+// token's own position.  tile(t0, m, last, step) queues what the caller adds around the tile's step and runs step(lm_mode) in
+// between -- exactly once: step is the tile's batched_step, and on the last tile the copies that keep the single-token state
+// coherent (logits / argmax of the last token).  A prompt of at most bt.cap tokens -- 2048, or seq_len when that is shorter --
+// is one tile.
+template <class Tile>
+int prompt_tiles(nl_engine *e, int stream, const int *tokens, int n, int pos0, const StepKnobs &k, Tile &&tile) {
+    nl_engine::Batch &b = e->bt;
+    for (int t0 = 0; t0 < n; t0 += b.cap) {
+        const int m = std::min(b.cap, n - t0);
+        HIPCK(e, hipStreamSynchronize(e->stream));  // (fill_meta; the caller's pinned per-tile staging follows the same rule)
+        for (int i = 0; i < m; i++) fill_meta(b, i, tokens[t0 + i], pos0 + t0 + i, stream);
+        const bool last = t0 + m == n;
+        auto step = [&](int lm_mode) -> int {
+            if (int rc = batched_step(e, b, e->stream, m, lm_mode, k, true)) return rc;
+            if (last) {
+                HIPCK(e, hipMemcpyAsync(e->logits, b.logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
+                HIPCK(e, hipMemcpyAsync(e->result, b.ids, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+            }
+            return NL_OK;
+        };
+        if (int rc = tile(t0, m, last, step)) return rc;
+    }
+    return NL_OK;
+}
+
+// every cached step graph -- whole-batch, sampled, mixed and sub-batch (they hold the device pointers of the step)
 void destroy_step_graphs(nl_engine *e) {
     auto drop = [](std::vector<nl_engine::StepGraph> &gs) { for (auto &G : gs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); } gs.clear(); };
     drop(e->bt_graphs);
     drop(e->bs_graphs);
-    for (auto &G : e->mx_graphs) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); }
-    e->mx_graphs.clear();
+    drop(e->mx_graphs);
     for (auto &sb : e->sub) drop(sb.graphs);
 }
 
@@ -3879,37 +3969,12 @@ int nl_prefill(nl_handle e, int stream, const int *tokens, int n, int pos0, floa
     if ((rc = note_positions(e, stream, pos0, n))) return rc;
     const StepKnobs k;
     if (n >= process_knobs().batch_min && batch_supported(e)) {
-        // multi-token path: 64-token tiles on the matrix cores; causality comes from each token's own pos
-        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc; }
-        nl_engine::Batch &b = e->bt;
-        for (int t0 = 0; t0 < n; t0 += b.cap) {
-            const int m = std::min(b.cap, n - t0);
-            HIPCK(e, hipStreamSynchronize(e->stream));  // h_meta is reused per tile
-            for (int i = 0; i < m; i++) {
-                b.h_meta[i] = tokens[t0 + i];
-                b.h_meta[b.cap + i] = pos0 + t0 + i;
-                b.h_meta[2 * b.cap + i] = stream;
-            }
-            const bool last = t0 + m == n;
-            if ((rc = batched_step(e, b, e->stream, m, last ? 2 : 0, k, true))) return rc;
-            if (last) {
-                // keep the single-token state coherent: logits / argmax of the last token
-                HIPCK(e, hipMemcpyAsync(e->logits, b.logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
-                HIPCK(e, hipMemcpyAsync(e->result, b.ids, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
-            }
-        }
+        // multi-token path: only the last tile needs its LM head
+        if ((rc = batch_ready(e, e->bt, k))) return rc;
+        if ((rc = prompt_tiles(e, stream, tokens, n, pos0, k, [](int, int, bool last, auto &step) { return step(last ? 2 : 0); }))) return rc;
     } else {
-        for (int attempt = 0;; attempt++) {
-            for (int i = 0; i < n; i++) {
-                int *c = e->h_ctl_ring + (size_t)i * CTL_WORDS;
-                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos0 + i; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = stream;
-                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
-                if ((rc = launch_step(e, pos0 + i))) return rc;
-            }
-            HIPCK(e, hipStreamSynchronize(e->stream));
-            if (attempt == 0 && take_fused_timeout(e)) continue;   // the prompt again, on the general plan
-            break;
-        }
+        auto row = [&](int i) { return StepRow{tokens[i], pos0 + i, stream}; };
+        if ((rc = single_steps(e, n, row, NoHook{}))) return rc;
     }
     if (last_logits_out)
         HIPCK(e, hipMemcpyAsync(e->h_logits, e->logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToHost, e->stream));
@@ -3962,28 +4027,17 @@ int nl_score(nl_handle e, int stream, const int *tokens, const int *targets, int
     const StepKnobs k;
     if (n >= process_knobs().batch_min && batch_supported(e)) {
         // nl_prefill's tiles, each with the scoring LM head (batched_step, lm_mode 3)
-        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k)) || (rc = score_alloc(e, e->bt, k))) return rc; }
+        if ((rc = batch_ready(e, e->bt, k, 2048, [&] { return score_alloc(e, e->bt, k); }))) return rc;
         nl_engine::Batch &b = e->bt;
-        for (int t0 = 0; t0 < n; t0 += b.cap) {
-            const int m = std::min(b.cap, n - t0);
-            HIPCK(e, hipStreamSynchronize(e->stream));  // h_meta and h_targets are reused per tile
-            for (int i = 0; i < m; i++) {
-                b.h_meta[i] = tokens[t0 + i];
-                b.h_meta[b.cap + i] = pos0 + t0 + i;
-                b.h_meta[2 * b.cap + i] = stream;
-                b.h_targets[i] = targets[t0 + i];
-            }
+        auto tile = [&](int t0, int m, bool last, auto &step) -> int {
+            for (int i = 0; i < m; i++) b.h_targets[i] = targets[t0 + i];
             HIPCK(e, hipMemcpyAsync(b.sc_targets, b.h_targets, (size_t)m * sizeof(int), hipMemcpyHostToDevice, e->stream));
-            const bool last = t0 + m == n;
-            if ((rc = batched_step(e, b, e->stream, m, last ? 3 : 4, k, true))) return rc;
-            if (last) {
-                HIPCK(e, hipMemcpyAsync(e->logits, b.logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
-                HIPCK(e, hipMemcpyAsync(e->result, b.ids, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
-            }
-            // (a text of at most b.cap tokens -- 2048, or seq_len when that is shorter -- is one tile: one read-back of its results)
+            if (int r2 = step(last ? 3 : 4)) return r2;
             HIPCK(e, hipMemcpyAsync(logprob_out + t0, b.sc_logprob, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
             if (argmax_out) HIPCK(e, hipMemcpyAsync(argmax_out + t0, b.sc_argmax, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-        }
+            return NL_OK;
+        };
+        if ((rc = prompt_tiles(e, stream, tokens, n, pos0, k, tile))) return rc;
     } else {
         // the single-token plan per token, each step's logits reduced where the step left them
         if (!e->sc_logprob) {
@@ -3993,19 +4047,13 @@ int nl_score(nl_handle e, int stream, const int *tokens, const int *targets, int
             HIPCK(e, dalloc(&e->sc_logprob, (size_t)e->cfg.seq_len, &e->bytes_state));
         }
         HIPCK(e, hipMemcpyAsync(e->sc_targets, targets, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
-        for (int attempt = 0;; attempt++) {
-            for (int i = 0; i < n; i++) {
-                int *c = e->h_ctl_ring + (size_t)i * CTL_WORDS;
-                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos0 + i; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = stream;
-                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
-                if ((rc = launch_step(e, pos0 + i))) return rc;
-                const ScoreRowsParams SP{e->logits, e->cfg.vocab, e->cfg.vocab, e->sc_targets + i, e->sc_logprob + i, nullptr, e->sc_argmax + i};
-                HIPCK(e, launch_score_rows(SP, 1, e->stream));
-            }
-            HIPCK(e, hipStreamSynchronize(e->stream));
-            if (attempt == 0 && take_fused_timeout(e)) continue;   // the prompt again, on the general plan: every result is rewritten
-            break;
-        }
+        auto row = [&](int i) { return StepRow{tokens[i], pos0 + i, stream}; };
+        auto score_row = [&](int i) -> int {
+            const ScoreRowsParams SP{e->logits, e->cfg.vocab, e->cfg.vocab, e->sc_targets + i, e->sc_logprob + i, nullptr, e->sc_argmax + i};
+            HIPCK(e, launch_score_rows(SP, 1, e->stream));
+            return NL_OK;
+        };
+        if ((rc = single_steps(e, n, row, score_row))) return rc;     // (a redo rewrites every result)
         HIPCK(e, hipMemcpyAsync(logprob_out, e->sc_logprob, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         if (argmax_out) HIPCK(e, hipMemcpyAsync(argmax_out, e->sc_argmax, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     }
@@ -4049,6 +4097,15 @@ int nl_op_score_rows(int device, const float *logits, int vocab, int n, const in
     return rc;
 }
 
+namespace {
+// a decode batch names a stream once: row i against the rows in front of it
+int check_stream_once(nl_engine *e, const int *streams, int i) {
+    for (int j = 0; j < i; j++)
+        if (streams[j] == streams[i]) return e->fail(NL_ERR_INVALID, "stream %d appears twice in one batch", streams[i]);
+    return NL_OK;
+}
+}  // namespace
+
 int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, float *logits_out,
                      int *next_ids) {
     if (e && e->grp) {
@@ -4062,9 +4119,7 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
     if (n > e->cfg.max_streams) return e->fail(NL_ERR_INVALID, "batch of %d exceeds max_streams %d", n, e->cfg.max_streams);
     int rc;
     for (int i = 0; i < n; i++) {
-        if ((rc = check_step_args(e, streams[i], tokens[i], pos[i]))) return rc;
-        for (int j = 0; j < i; j++)
-            if (streams[j] == streams[i]) return e->fail(NL_ERR_INVALID, "stream %d appears twice in one batch", streams[i]);
+        if ((rc = check_step_args(e, streams[i], tokens[i], pos[i])) || (rc = check_stream_once(e, streams, i))) return rc;
     }
     if (n == 0) return NL_OK;
     HIPCK(e, hipSetDevice(e->dev));
@@ -4087,7 +4142,7 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
                 const int m = std::min(per, n - t0);
                 if (m <= 0) break;
                 nl_engine::SubBatch &sb = e->sub[g];
-                { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, sb.bt, QG_TOK)) || (rc = dgemm_prepare(e, k))) return rc; }
+                if ((rc = batch_ready(e, sb.bt, k, QG_TOK))) return rc;
                 if (!sb.st) {
                     HIPCK(e, hipStreamCreateWithFlags(&sb.st, hipStreamNonBlocking));
                     HIPCK(e, hipEventCreateWithFlags(&sb.done, hipEventDisableTiming));
@@ -4113,11 +4168,11 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
             HIPCK(e, hipStreamSynchronize(e->stream));
             return NL_OK;
         }
-        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc; }
+        if ((rc = batch_ready(e, e->bt, k))) return rc;
         nl_engine::Batch &b = e->bt;
         for (int t0 = 0; t0 < n; t0 += b.lm_cap) {
             const int m = std::min(b.lm_cap, n - t0);
-            HIPCK(e, hipStreamSynchronize(e->stream));     // (h_meta is reused per chunk)
+            HIPCK(e, hipStreamSynchronize(e->stream));
             if ((rc = decode_step(e, b, e->bt_graphs, e->stream, streams + t0, tokens + t0, pos + t0, m, k))) return rc;
             if (logits_out)
                 HIPCK(e, hipMemcpyAsync(logits_out + (size_t)t0 * e->cfg.vocab, b.logits, (size_t)m * e->cfg.vocab * 4,
@@ -4127,27 +4182,21 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
         HIPCK(e, hipStreamSynchronize(e->stream));
         return NL_OK;
     }
-    for (int attempt = 0;; attempt++) {
-        for (int i = 0; i < n; i++) {
-            int *c = e->h_ctl_ring + (size_t)i * CTL_WORDS;
-            c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos[i]; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = streams[i];
-            HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
-            if ((rc = launch_step(e, pos[i]))) return rc;
-            if (logits_out)
-                HIPCK(e, hipMemcpyAsync(logits_out + (size_t)i * e->cfg.vocab, e->logits, (size_t)e->cfg.vocab * 4,
-                                        hipMemcpyDeviceToHost, e->stream));
-            if (next_ids) HIPCK(e, hipMemcpyAsync(next_ids + i, e->result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-        }
-        HIPCK(e, hipStreamSynchronize(e->stream));
-        if (attempt == 0 && take_fused_timeout(e)) continue;   // every stream's step again, on the general plan
-        break;
-    }
-    return NL_OK;
+    auto row = [&](int i) { return StepRow{tokens[i], pos[i], streams[i]}; };
+    auto read_back = [&](int i) -> int {
+        if (logits_out)
+            HIPCK(e, hipMemcpyAsync(logits_out + (size_t)i * e->cfg.vocab, e->logits, (size_t)e->cfg.vocab * 4,
+                                    hipMemcpyDeviceToHost, e->stream));
+        if (next_ids) HIPCK(e, hipMemcpyAsync(next_ids + i, e->result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        return NL_OK;
+    };
+    return single_steps(e, n, row, read_back);
 }
 
 namespace {
 
-constexpr int BS_MAX_ROWS = QG_TOK;   // rows of one nl_forward_batch_sample call: the LM head's batch
+constexpr int BS_MAX_ROWS = QG_TOK;       // rows of one nl_forward_batch_sample call: the LM head's batch
+constexpr int SAMP_MAX_VOCAB = 131072;    // the largest vocabulary the sampler's kernels cover
 
 // The block of an nl_forward_batch_sample call of m rows, in 32-bit words: settings [m][8] (SampRow) | uniforms [m] | window
 // lengths [m] | ids [m] | windows [m][1024].  Uploaded whole at the head of the step, read back from the window lengths on.
@@ -4156,6 +4205,47 @@ BsLayout bs_layout(int m) {
     const size_t M = (size_t)m;
     return {0, 8 * M, 9 * M, 10 * M, 11 * M, (11 + (size_t)SAMP_THREADS) * M};
 }
+
+// the per-row arguments of a sampled call: settings, uniforms, windows (row i's at recent + i * recent_stride) and their lengths
+struct SampleRows { const nl_sample_params *params; const float *uniforms; int *recent; int recent_stride; int *n_recent; };
+
+// row i of a sampled call: its settings, then its window against the caller's stride and the settings (e == nullptr: bare codes)
+int check_sample_row(nl_engine *e, int i, const SampleRows &r) {
+    const nl_sample_params &p = r.params[i];
+    if (int rc = check_sample_params(e, &p)) return rc;
+    if (p.rep_window > r.recent_stride)
+        return e ? e->fail(NL_ERR_INVALID, "rep_window %d of row %d exceeds recent_stride %d", p.rep_window, i, r.recent_stride) : (int)NL_ERR_INVALID;
+    if (r.n_recent[i] < 0 || r.n_recent[i] > p.rep_window)
+        return e ? e->fail(NL_ERR_INVALID, "n_recent %d of row %d exceeds rep_window %d", r.n_recent[i], i, p.rep_window) : (int)NL_ERR_INVALID;
+    return NL_OK;
+}
+
+// A call's block in host memory (the handle's pinned h_bs, or the op's own): packed from the caller's first n rows, copied to the
+// device whole, copied back from the window lengths on, unpacked into the caller's ids, lengths and windows.  Every call brings
+// its settings, uniforms and windows again: nothing but KV rows and position marks outlives it.
+struct SampBlock {
+    BsLayout L;
+    int *h;
+    void pack(const SampleRows &r, int n) const {
+        for (int i = 0; i < n; i++) {
+            reinterpret_cast<SampRow *>(h + L.rows)[i] = samp_row_of(r.params[i]);
+            reinterpret_cast<float *>(h + L.u)[i] = r.uniforms[i];
+            h[L.nrec + i] = r.n_recent[i];
+            memcpy(h + L.win + (size_t)i * SAMP_THREADS, r.recent + (size_t)i * r.recent_stride, (size_t)r.n_recent[i] * 4);
+        }
+    }
+    hipError_t upload(int *dev, hipStream_t st) const { return hipMemcpyAsync(dev, h, L.total * 4, hipMemcpyHostToDevice, st); }
+    hipError_t download(int *dev, hipStream_t st) const {
+        return hipMemcpyAsync(h + L.nrec, dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, st);
+    }
+    void unpack(const SampleRows &r, int n, int *ids) const {
+        for (int i = 0; i < n; i++) {
+            ids[i] = h[L.ids + i];
+            r.n_recent[i] = h[L.nrec + i];
+            memcpy(r.recent + (size_t)i * r.recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)r.n_recent[i] * 4);
+        }
+    }
+};
 
 // the sampler over rows [row0, row0 + nrows) of the block `blk` (m rows), row r's logits at logits + (r - row0) * vocab; the
 // scratch slabs of s (a sampler of BS_MAX_ROWS rows) are taken from slab 0.  Shared by nl_forward_batch_sample and
@@ -4195,101 +4285,49 @@ int nl_forward_batch_sample(nl_handle e, const int *streams, const int *tokens, 
         return NL_ERR_INVALID;
     if (n > e->cfg.max_streams) return e->fail(NL_ERR_INVALID, "batch of %d exceeds max_streams %d", n, e->cfg.max_streams);
     if (n > BS_MAX_ROWS) return e->fail(NL_ERR_INVALID, "sampled batch of %d exceeds %d rows", n, BS_MAX_ROWS);
-    if (e->cfg.vocab > 131072) return e->fail(NL_ERR_UNSUPPORTED, "on-device sampling covers vocabularies up to 131072, not %d", e->cfg.vocab);
+    if (e->cfg.vocab > SAMP_MAX_VOCAB) return e->fail(NL_ERR_UNSUPPORTED, "on-device sampling covers vocabularies up to %d, not %d", SAMP_MAX_VOCAB, e->cfg.vocab);
+    const SampleRows rows{params, uniforms, recent, recent_stride, n_recent};
     int rc;
-    for (int i = 0; i < n; i++) {
-        if ((rc = check_step_args(e, streams[i], tokens[i], pos[i]))) return rc;
-        for (int j = 0; j < i; j++)
-            if (streams[j] == streams[i]) return e->fail(NL_ERR_INVALID, "stream %d appears twice in one batch", streams[i]);
-        if ((rc = check_sample_params(e, &params[i]))) return rc;
-        if (params[i].rep_window > recent_stride)
-            return e->fail(NL_ERR_INVALID, "rep_window %d of row %d exceeds recent_stride %d", params[i].rep_window, i, recent_stride);
-        if (n_recent[i] < 0 || n_recent[i] > params[i].rep_window)
-            return e->fail(NL_ERR_INVALID, "n_recent %d of row %d exceeds rep_window %d", n_recent[i], i, params[i].rep_window);
-    }
+    for (int i = 0; i < n; i++)
+        if ((rc = check_step_args(e, streams[i], tokens[i], pos[i])) || (rc = check_stream_once(e, streams, i)) || (rc = check_sample_row(e, i, rows))) return rc;
     if (n == 0) return NL_OK;
     HIPCK(e, hipSetDevice(e->dev));
     if (int qrc = pd_session_close(e)) return qrc;
     if ((rc = bs_prepare(e))) return rc;
     for (int i = 0; i < n; i++)
         if ((rc = note_positions(e, streams[i], pos[i], 1))) return rc;
-    // every call brings its settings, uniforms and windows again: nothing but KV rows and position marks outlives it
-    const BsLayout L = bs_layout(n);
-    int *const h = e->h_bs;
-    auto pack = [&]() {
-        for (int i = 0; i < n; i++) {
-            reinterpret_cast<SampRow *>(h + L.rows)[i] = samp_row_of(params[i]);
-            reinterpret_cast<float *>(h + L.u)[i] = uniforms[i];
-            h[L.nrec + i] = n_recent[i];
-            memcpy(h + L.win + (size_t)i * SAMP_THREADS, recent + (size_t)i * recent_stride, (size_t)n_recent[i] * 4);
-        }
-    };
-    auto upload = [&](hipStream_t st) { return hipMemcpyAsync(e->bs_dev, h, L.total * 4, hipMemcpyHostToDevice, st); };
-    auto download = [&](hipStream_t st) {
-        return hipMemcpyAsync(h + L.nrec, e->bs_dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, st);
-    };
+    const SampBlock blk{bs_layout(n), e->h_bs};
     const StepKnobs k;
     if (n >= process_knobs().batch_min && batch_supported(e)) {
         // one batched_step with every row's logits (lm_mode 1), the n-row sampler on them, the block in and out around it: one
-        // graph per (rows, position splits, step knobs) -- the settings are data, so any mix of them replays the same graph
-        { std::lock_guard<std::mutex> setup(g_setup_mu); if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc; }
+        // graph per step key -- the settings are data, so any mix of them replays the same graph
+        if ((rc = batch_ready(e, e->bt, k))) return rc;
         nl_engine::Batch &b = e->bt;
         int nsplit = 1;
-        for (int i = 0; i < n; i++) {
-            b.h_meta[i] = tokens[i];
-            b.h_meta[b.cap + i] = pos[i];
-            b.h_meta[2 * b.cap + i] = streams[i];
-            nsplit = std::max(nsplit, pos[i] / ATT_CH + 1);
-        }
-        pack();
+        for (int i = 0; i < n; i++) nsplit = std::max(nsplit, fill_meta(b, i, tokens[i], pos[i], streams[i]));
+        blk.pack(rows, n);
         auto body = [&](hipStream_t st) -> int {
-            HIPCK(e, upload(st));
+            HIPCK(e, blk.upload(e->bs_dev, st));
             if (int r2 = batched_step(e, b, st, n, 1, k)) return r2;
             HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n, 0, n, b.logits, 7u, st));
-            HIPCK(e, download(st));
+            HIPCK(e, blk.download(e->bs_dev, st));
             return NL_OK;
         };
-        hipGraphExec_t exec = nullptr;
-        for (const auto &G : e->bs_graphs)
-            if (G.m == n && G.nsplit == nsplit && G.knobs == k) exec = G.exec;
-        if (!exec && e->use_graph) {
-            std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
-            hipGraph_t gr = nullptr;
-            if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int r2 = body(e->stream);
-                const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
-                if (!r2 && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess)
-                    e->bs_graphs.push_back({n, nsplit, k, gr, exec});
-                else { if (gr) (void)hipGraphDestroy(gr); exec = nullptr; }
-            }
-            (void)hipGetLastError();
-        }
-        if (exec) HIPCK(e, hipGraphLaunch(exec, e->stream));
-        else if ((rc = body(e->stream))) return rc;       // (no graphs, or a step whose capture failed: eager)
+        if ((rc = run_step_graph(e, e->bs_graphs, {n, n, n, 0, nsplit, true, k}, e->stream, SIZE_MAX, body))) return rc;
         HIPCK(e, hipStreamSynchronize(e->stream));
     } else {
         // fewer rows, or a format outside the batch path: every row's single-token step, then the sampler on that row's logits
-        for (int attempt = 0;; attempt++) {
-            pack();
-            HIPCK(e, upload(e->stream));
-            for (int i = 0; i < n; i++) {
-                int *c = e->h_ctl_ring + (size_t)i * CTL_WORDS;
-                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos[i]; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = streams[i];
-                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
-                if ((rc = launch_step(e, pos[i]))) return rc;
-                HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n, i, 1, e->logits, 1u << samp_mode(params[i].temperature, params[i].top_p), e->stream));
-            }
-            HIPCK(e, download(e->stream));
-            HIPCK(e, hipStreamSynchronize(e->stream));
-            if (attempt == 0 && take_fused_timeout(e)) continue;   // every row again, on the general plan, from the caller's windows
-            break;
-        }
+        // (a redo starts from the caller's windows again)
+        auto row = [&](int i) { return StepRow{tokens[i], pos[i], streams[i]}; };
+        auto block_in = [&]() -> int { blk.pack(rows, n); HIPCK(e, blk.upload(e->bs_dev, e->stream)); return NL_OK; };
+        auto sample_row = [&](int i) -> int {
+            HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n, i, 1, e->logits, 1u << samp_mode(params[i].temperature, params[i].top_p), e->stream));
+            return NL_OK;
+        };
+        auto block_out = [&]() -> int { HIPCK(e, blk.download(e->bs_dev, e->stream)); return NL_OK; };
+        if ((rc = single_steps(e, n, row, sample_row, block_in, block_out))) return rc;
     }
-    for (int i = 0; i < n; i++) {
-        next_ids[i] = h[L.ids + i];
-        n_recent[i] = h[L.nrec + i];
-        memcpy(recent + (size_t)i * recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)n_recent[i] * 4);
-    }
+    blk.unpack(rows, n, next_ids);
     return NL_OK;
 }
 
@@ -4302,11 +4340,9 @@ int mixed_max_rows(const nl_engine *e) {     // min(MX_MAX_ROWS, Batch::cap) wit
     return std::min(MX_MAX_ROWS, ((e->cfg.seq_len + QG_TOK - 1) / QG_TOK) * QG_TOK);
 }
 
-struct MixedSample { const nl_sample_params *params; const float *uniforms; int *recent; int recent_stride; int *n_recent; };
-
 // nl_forward_mixed / nl_forward_mixed_sample (sm != null)
 int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, int n_out, float *logits_out,
-                  int *next_ids, const MixedSample *sm) {
+                  int *next_ids, const SampleRows *sm) {
     const char *const who = sm ? "nl_forward_mixed_sample" : "nl_forward_mixed";
     if (!e) return NL_ERR_INVALID;
     if (e->grp) return e->fail(NL_ERR_UNSUPPORTED, "%s: device groups are not supported", who);
@@ -4317,7 +4353,7 @@ int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int 
     if (n_out < 0 || n_out > n) return e->fail(NL_ERR_INVALID, "%s: n_out %d outside [0, n = %d]", who, n_out, n);
     if (n_out > BS_MAX_ROWS) return e->fail(NL_ERR_INVALID, "%s: n_out %d exceeds the LM head's batch of %d rows", who, n_out, BS_MAX_ROWS);
     if (n > mixed_max_rows(e)) return e->fail(NL_ERR_INVALID, "%s: step of %d rows exceeds %d", who, n, mixed_max_rows(e));
-    if (sm && e->cfg.vocab > 131072) return e->fail(NL_ERR_UNSUPPORTED, "on-device sampling covers vocabularies up to 131072, not %d", e->cfg.vocab);
+    if (sm && e->cfg.vocab > SAMP_MAX_VOCAB) return e->fail(NL_ERR_UNSUPPORTED, "on-device sampling covers vocabularies up to %d, not %d", SAMP_MAX_VOCAB, e->cfg.vocab);
     int rc;
     // per stream: one gap-free run of distinct positions, ascending among the output rows and among the other rows (an output
     // row sits in front of the chunk that ends just below it: the two parts of the arrays are ordered each on its own)
@@ -4346,13 +4382,8 @@ int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int 
         if (R.hi - R.lo + 1 != R.k)
             return e->fail(NL_ERR_INVALID, "%s: stream %d: %d rows over positions %d..%d (the rows of a stream are one run without gaps)",
                            who, R.stream, R.k, R.lo, R.hi);
-    for (int i = 0; sm && i < n_out; i++) {
-        if ((rc = check_sample_params(e, &sm->params[i]))) return rc;
-        if (sm->params[i].rep_window > sm->recent_stride)
-            return e->fail(NL_ERR_INVALID, "rep_window %d of row %d exceeds recent_stride %d", sm->params[i].rep_window, i, sm->recent_stride);
-        if (sm->n_recent[i] < 0 || sm->n_recent[i] > sm->params[i].rep_window)
-            return e->fail(NL_ERR_INVALID, "n_recent %d of row %d exceeds rep_window %d", sm->n_recent[i], i, sm->params[i].rep_window);
-    }
+    for (int i = 0; sm && i < n_out; i++)
+        if ((rc = check_sample_row(e, i, *sm))) return rc;
     if (n == 0) return NL_OK;
     // a decode batch: the existing path, bit for bit
     if (!repeats && n_out == n)
@@ -4363,32 +4394,17 @@ int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int 
     if (sm && n_out > 0 && (rc = bs_prepare(e))) return rc;
     const StepKnobs k;
     const bool multi = n >= process_knobs().batch_min && batch_supported(e);
-    if (multi) {
-        std::lock_guard<std::mutex> setup(g_setup_mu);
-        if ((rc = batch_alloc(e, e->bt)) || (rc = dgemm_prepare(e, k))) return rc;
-        if (n > e->bt.cap) return e->fail(NL_ERR_INVALID, "%s: step of %d rows exceeds %d", who, n, e->bt.cap);
-    }
+    if (multi && (rc = batch_ready(e, e->bt, k, 2048, [&] {
+            return n > e->bt.cap ? e->fail(NL_ERR_INVALID, "%s: step of %d rows exceeds %d", who, n, e->bt.cap) : (int)NL_OK;
+        }))) return rc;
     for (const Run &r : runs)
         if ((rc = note_positions(e, r.stream, r.lo, r.k))) return rc;
     const size_t V = (size_t)e->cfg.vocab;
-    const BsLayout L = bs_layout(std::max(n_out, 1));
-    int *const h = e->h_bs;
-    auto pack = [&]() {
-        for (int i = 0; sm && i < n_out; i++) {
-            reinterpret_cast<SampRow *>(h + L.rows)[i] = samp_row_of(sm->params[i]);
-            reinterpret_cast<float *>(h + L.u)[i] = sm->uniforms[i];
-            h[L.nrec + i] = sm->n_recent[i];
-            memcpy(h + L.win + (size_t)i * SAMP_THREADS, sm->recent + (size_t)i * sm->recent_stride, (size_t)sm->n_recent[i] * 4);
-        }
-    };
+    const SampBlock blk{bs_layout(std::max(n_out, 1)), e->h_bs};
     const bool sampled = sm && n_out > 0;
     if (multi) {
         nl_engine::Batch &b = e->bt;
-        for (int i = 0; i < n; i++) {
-            b.h_meta[i] = tokens[i];
-            b.h_meta[b.cap + i] = pos[i];
-            b.h_meta[2 * b.cap + i] = streams[i];
-        }
+        for (int i = 0; i < n; i++) fill_meta(b, i, tokens[i], pos[i], streams[i]);
         // The attention plan.  Output rows and the single rows right behind them: the per-token kernel.  From there on every
         // run of adjacent rows of one stream at consecutive positions is a segment, cut into query tiles; a tile and a
         // 128-key chunk it can see make one entry of the work list (attn_seg_kernel, nl_batch.h).  The list lives where a
@@ -4425,34 +4441,17 @@ int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int 
         }
         int ns_tok = 1;
         for (int i = 0; i < mp.n_tok; i++) ns_tok = std::max(ns_tok, pos[i] / ATT_CH + 1);
-        pack();
+        if (sampled) blk.pack(*sm, n_out);
         auto body = [&](hipStream_t st) -> int {
-            if (sampled) HIPCK(e, hipMemcpyAsync(e->bs_dev, h, L.total * 4, hipMemcpyHostToDevice, st));
+            if (sampled) HIPCK(e, blk.upload(e->bs_dev, st));
             if (int r2 = batched_step(e, b, st, n, 1, k, false, &mp)) return r2;
             if (sampled) {
                 HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n_out, 0, n_out, b.logits, 7u, st));
-                HIPCK(e, hipMemcpyAsync(h + L.nrec, e->bs_dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, st));
+                HIPCK(e, blk.download(e->bs_dev, st));
             }
             return NL_OK;
         };
-        hipGraphExec_t exec = nullptr;
-        for (const auto &G : e->mx_graphs)
-            if (G.n == n && G.n_out == n_out && G.n_tok == mp.n_tok && G.n_work == mp.n_work && G.ns_tok == ns_tok && G.sampled == sampled && G.knobs == k)
-                exec = G.exec;
-        if (!exec && e->use_graph && (int)e->mx_graphs.size() < MX_MAX_GRAPHS) {
-            std::lock_guard<std::mutex> setup(g_setup_mu);      // (a capture must not overlap another thread's allocations)
-            hipGraph_t gr = nullptr;
-            if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int r2 = body(e->stream);
-                const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
-                if (!r2 && ce == hipSuccess && gr && hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0) == hipSuccess)
-                    e->mx_graphs.push_back({n, n_out, mp.n_tok, mp.n_work, ns_tok, sampled, k, gr, exec});
-                else { if (gr) (void)hipGraphDestroy(gr); exec = nullptr; }
-            }
-            (void)hipGetLastError();
-        }
-        if (exec) HIPCK(e, hipGraphLaunch(exec, e->stream));
-        else if ((rc = body(e->stream))) return rc;
+        if ((rc = run_step_graph(e, e->mx_graphs, {n, n_out, mp.n_tok, mp.n_work, ns_tok, sampled, k}, e->stream, MX_MAX_GRAPHS, body))) return rc;
         if (logits_out && n_out > 0) HIPCK(e, hipMemcpyAsync(logits_out, b.logits, (size_t)n_out * V * 4, hipMemcpyDeviceToHost, e->stream));
         if (!sm && next_ids && n_out > 0) HIPCK(e, hipMemcpyAsync(next_ids, b.ids, (size_t)n_out * sizeof(int), hipMemcpyDeviceToHost, e->stream));
         HIPCK(e, hipStreamSynchronize(e->stream));
@@ -4462,32 +4461,27 @@ int forward_mixed(nl_handle e, const int *streams, const int *tokens, const int 
         std::vector<int> order((size_t)n);
         for (int i = 0; i < n; i++) order[i] = i;
         std::stable_sort(order.begin(), order.end(), [&](int a, int c2) { return streams[a] != streams[c2] ? streams[a] < streams[c2] : pos[a] < pos[c2]; });
-        for (int attempt = 0;; attempt++) {
-            pack();
-            if (sampled) HIPCK(e, hipMemcpyAsync(e->bs_dev, h, L.total * 4, hipMemcpyHostToDevice, e->stream));
-            for (int j = 0; j < n; j++) {
-                const int i = order[j], slot = j % e->ctl_ring_cap;
-                if (j > 0 && slot == 0) HIPCK(e, hipStreamSynchronize(e->stream));      // (the ring of control blocks is reused)
-                int *c = e->h_ctl_ring + (size_t)slot * CTL_WORDS;
-                c[CTL_TOKEN] = tokens[i]; c[CTL_POS] = pos[i]; c[CTL_CHAIN] = 0; c[CTL_STEP] = 0; c[CTL_STREAM] = streams[i];
-                HIPCK(e, hipMemcpyAsync(e->ctl, c, CTL_WORDS * sizeof(int), hipMemcpyHostToDevice, e->stream));
-                if ((rc = launch_step(e, pos[i]))) return rc;
-                if (i >= n_out) continue;
-                if (logits_out) HIPCK(e, hipMemcpyAsync(logits_out + (size_t)i * V, e->logits, V * 4, hipMemcpyDeviceToHost, e->stream));
-                if (!sm && next_ids) HIPCK(e, hipMemcpyAsync(next_ids + i, e->result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-                if (sm) HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n_out, i, 1, e->logits, 1u << samp_mode(sm->params[i].temperature, sm->params[i].top_p), e->stream));
-            }
-            if (sampled) HIPCK(e, hipMemcpyAsync(h + L.nrec, e->bs_dev + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost, e->stream));
-            HIPCK(e, hipStreamSynchronize(e->stream));
-            if (attempt == 0 && take_fused_timeout(e)) continue;   // every row again, on the general plan, from the caller's windows
-            break;
-        }
+        // (a redo starts from the caller's windows again)
+        auto row = [&](int j) { const int i = order[j]; return StepRow{tokens[i], pos[i], streams[i]}; };
+        auto block_in = [&]() -> int {
+            if (sampled) { blk.pack(*sm, n_out); HIPCK(e, blk.upload(e->bs_dev, e->stream)); }
+            return NL_OK;
+        };
+        auto output_row = [&](int j) -> int {
+            const int i = order[j];
+            if (i >= n_out) return NL_OK;
+            if (logits_out) HIPCK(e, hipMemcpyAsync(logits_out + (size_t)i * V, e->logits, V * 4, hipMemcpyDeviceToHost, e->stream));
+            if (!sm && next_ids) HIPCK(e, hipMemcpyAsync(next_ids + i, e->result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+            if (sm) HIPCK(e, launch_block_sample(e->bs, e->cfg.vocab, e->bs_dev, n_out, i, 1, e->logits, 1u << samp_mode(sm->params[i].temperature, sm->params[i].top_p), e->stream));
+            return NL_OK;
+        };
+        auto block_out = [&]() -> int {
+            if (sampled) HIPCK(e, blk.download(e->bs_dev, e->stream));
+            return NL_OK;
+        };
+        if ((rc = single_steps(e, n, row, output_row, block_in, block_out))) return rc;
     }
-    for (int i = 0; sm && i < n_out; i++) {
-        next_ids[i] = h[L.ids + i];
-        sm->n_recent[i] = h[L.nrec + i];
-        memcpy(sm->recent + (size_t)i * sm->recent_stride, h + L.win + (size_t)i * SAMP_THREADS, (size_t)sm->n_recent[i] * 4);
-    }
+    if (sampled) blk.unpack(*sm, n_out, next_ids);
     return NL_OK;
 }
 
@@ -4500,7 +4494,7 @@ int nl_forward_mixed(nl_handle e, const int *streams, const int *tokens, const i
 int nl_forward_mixed_sample(nl_handle e, const int *streams, const int *tokens, const int *pos, int n, int n_out,
                             const nl_sample_params *params, const float *uniforms, int *recent, int recent_stride, int *n_recent,
                             int *next_ids) {
-    const MixedSample sm{params, uniforms, recent, recent_stride, n_recent};
+    const SampleRows sm{params, uniforms, recent, recent_stride, n_recent};
     return forward_mixed(e, streams, tokens, pos, n, n_out, nullptr, next_ids, &sm);
 }
 
@@ -4517,21 +4511,16 @@ int nl_op_sample_rows(int device, float *logits, int vocab, int n, const nl_samp
                       int *recent, int recent_stride, int *n_recent, int *picked) {
     if (!logits || vocab <= 0 || n < 1 || n > BS_MAX_ROWS || !params || !uniforms || !recent || !n_recent || !picked)
         return NL_ERR_INVALID;
-    if (vocab > 131072) return NL_ERR_UNSUPPORTED;
-    for (int i = 0; i < n; i++) {
-        if (int rc = check_sample_params(nullptr, &params[i])) return rc;
-        if (params[i].rep_window > recent_stride || n_recent[i] < 0 || n_recent[i] > params[i].rep_window) return NL_ERR_INVALID;
-    }
+    if (vocab > SAMP_MAX_VOCAB) return NL_ERR_UNSUPPORTED;
+    const SampleRows rows{params, uniforms, recent, recent_stride, n_recent};
+    for (int i = 0; i < n; i++)
+        if (int rc = check_sample_row(nullptr, i, rows)) return rc;
     if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    // the block of nl_forward_batch_sample, packed the same way
+    // the block of nl_forward_batch_sample, in pageable memory
     const BsLayout L = bs_layout(n);
     std::vector<int> h(L.total, 0);
-    for (int i = 0; i < n; i++) {
-        reinterpret_cast<SampRow *>(h.data() + L.rows)[i] = samp_row_of(params[i]);
-        reinterpret_cast<float *>(h.data() + L.u)[i] = uniforms[i];
-        h[L.nrec + i] = n_recent[i];
-        memcpy(h.data() + L.win + (size_t)i * SAMP_THREADS, recent + (size_t)i * recent_stride, (size_t)n_recent[i] * 4);
-    }
+    const SampBlock blk{L, h.data()};
+    blk.pack(rows, n);
     const size_t lg_bytes = (size_t)n * vocab * 4;
     SampScratch s;
     float *d_logits = nullptr;
@@ -4550,16 +4539,12 @@ int nl_op_sample_rows(int device, float *logits, int vocab, int n, const nl_samp
         if (hipMemset(s.h1g, 0xFF, (size_t)2048 * 8 * BS_MAX_ROWS) != hipSuccess) break;
         if (hipMemset2D(s.keys_in, kstride * 4, 0xFF, (size_t)vocab * 4, BS_MAX_ROWS) != hipSuccess) break;
         if (hipMemcpy(d_logits, logits, lg_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_blk, h.data(), L.total * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (blk.upload(d_blk, (hipStream_t)0) != hipSuccess) break;
         if (launch_block_sample(s, vocab, d_blk, n, 0, n, d_logits, 7u, (hipStream_t)0) != hipSuccess) break;
         if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(h.data() + L.nrec, d_blk + L.nrec, (L.total - L.nrec) * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (blk.download(d_blk, (hipStream_t)0) != hipSuccess || hipStreamSynchronize((hipStream_t)0) != hipSuccess) break;
         if (hipMemcpy(logits, d_logits, lg_bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
-        for (int i = 0; i < n; i++) {
-            picked[i] = h[L.ids + i];
-            n_recent[i] = h[L.nrec + i];
-            memcpy(recent + (size_t)i * recent_stride, h.data() + L.win + (size_t)i * SAMP_THREADS, (size_t)n_recent[i] * 4);
-        }
+        blk.unpack(rows, n, picked);
         rc = NL_OK;
     } while (0);
     samp_free(s);

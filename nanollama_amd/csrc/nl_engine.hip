@@ -479,10 +479,8 @@ struct nl_engine {
         uint8_t *embd_q8 = nullptr;  // token_embd of a Q4_0 / Q5_0 file re-blocked as Q8_0 for the in-launch lookup
         uint4 *wimg = nullptr, *lmimg = nullptr;
         unsigned short *simg = nullptr, *lmsimg = nullptr;
-        pd_u64 *gx = nullptr, *gqkv = nullptr, *go = nullptr, *gxp = nullptr;
-        pd_u32x4 *gh = nullptr;          // h: 16-byte granules (pd_h_row)
-        pd_u64 *gpart = nullptr;
-        pd_u32x4 *gam = nullptr;
+        pd_u32x4 *arena = nullptr;   // every hand-off area of a launch (pd_arena): one allocation, one memset
+        size_t arena_bytes = 0;
         unsigned *census = nullptr, *status = nullptr, *h_status = nullptr;
         float *norms = nullptr;      // [L][2][D] + [D]: attn_norm | ffn_norm of every layer, output_norm (one pointer for the kernel)
         unsigned tag_base = 0;
@@ -496,7 +494,6 @@ struct nl_engine {
         bool s_logits = false;       // ... whose LM-head units store every step's logits into h_logits
         int s_stream = 0, s_next_pos = 0, s_step = 0, s_nsteps = 0;
         pd_u64 *h_mail = nullptr, *d_mail = nullptr;   // pinned: [0] mailbox, [8] done word (own cache lines); device view
-        pd_u64 *gtok = nullptr;
         unsigned launch_no = 0;
         long long sessions = 0;
     } pd;
@@ -1505,7 +1502,7 @@ void pd_free_raw(nl_engine *e) {
 void pd_free(nl_engine *e) {
     pd_free_raw(e);
     nl_engine::Persist &d = e->pd;
-    void *bufs[] = {d.wimg, d.lmimg, d.simg, d.lmsimg, d.gx, d.gqkv, d.go, d.gxp, d.gh, d.gam, d.census, d.status, d.dbg, d.norms, d.gtok, d.gpart, d.embd_q8};
+    void *bufs[] = {d.wimg, d.lmimg, d.simg, d.lmsimg, d.arena, d.census, d.status, d.dbg, d.norms, d.embd_q8};
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (d.h_status) (void)hipHostFree(d.h_status);
     if (d.h_mail) (void)hipHostFree(d.h_mail);
@@ -1548,19 +1545,9 @@ int pd_build(nl_engine *e) {
     HIPCK(e, hipGetLastError());
     HIPCK(e, hipStreamSynchronize(e->stream));
     pd_free_raw(e);
-    const size_t L1 = (size_t)c.n_layers + 1;
-    HIPCK(e, dalloc(&d.gx, L1 * c.dim, &e->bytes_state));
-    HIPCK(e, dalloc(&d.go, L1 * c.dim, &e->bytes_state));
-    HIPCK(e, dalloc(&d.gqkv, L1 * 3 * c.dim, &e->bytes_state));
-    HIPCK(e, hipMemset(d.gqkv, 0, L1 * 3 * c.dim * 8));
-    HIPCK(e, dalloc(&d.gxp, L1 * c.dim, &e->bytes_state));
-    const size_t hgran = L1 * (size_t)(c.interm / pd_h_vpg(c.interm));       // (L + 1) * S granules of 16 bytes
-    HIPCK(e, dalloc(&d.gh, hgran, &e->bytes_state));
-    HIPCK(e, dalloc(&d.gam, (size_t)PD_GRID, &e->bytes_state));
-    HIPCK(e, dalloc(&d.gpart, (size_t)c.n_layers * c.n_heads * (PD_PARTS - 1) * 66, &e->bytes_state));
-    HIPCK(e, hipMemset(d.gpart, 0, (size_t)c.n_layers * c.n_heads * (PD_PARTS - 1) * 66 * 8));
-    HIPCK(e, hipMemset(d.gx, 0, L1 * c.dim * 8)); HIPCK(e, hipMemset(d.go, 0, L1 * c.dim * 8)); HIPCK(e, hipMemset(d.gxp, 0, L1 * c.dim * 8));
-    HIPCK(e, hipMemset(d.gh, 0, hgran * 16)); HIPCK(e, hipMemset(d.gam, 0, (size_t)PD_GRID * 16));
+    d.arena_bytes = pd_arena(c.dim, c.interm, c.n_heads, PD_MAXL).total;         // every granule area (the kernel's resource spans PD_MAXL layers): tag 0 everywhere
+    HIPCK(e, dalloc(&d.arena, d.arena_bytes / 16, &e->bytes_state));
+    HIPCK(e, hipMemset(d.arena, 0, d.arena_bytes));
     HIPCK(e, dalloc(&d.norms, ((size_t)c.n_layers * 2 + 1) * c.dim, &e->bytes_state));
     for (int l = 0; l < c.n_layers; l++) {
         HIPCK(e, hipMemcpy(d.norms + (size_t)(2 * l) * c.dim, e->layers[l].attn_norm, (size_t)c.dim * 4, hipMemcpyDeviceToDevice));
@@ -1569,8 +1556,6 @@ int pd_build(nl_engine *e) {
     HIPCK(e, hipMemcpy(d.norms + (size_t)(2 * c.n_layers) * c.dim, e->output_norm, (size_t)c.dim * 4, hipMemcpyDeviceToDevice));
     HIPCK(e, dalloc(&d.census, (size_t)32, &e->bytes_state));       // two launches' words, used alternately (each launch zeroes the other's)
     HIPCK(e, hipMemset(d.census, 0, 32 * sizeof(unsigned)));
-    HIPCK(e, dalloc(&d.gtok, (size_t)2, &e->bytes_state));
-    HIPCK(e, hipMemset(d.gtok, 0, 16));
     HIPCK(e, hipHostMalloc((void **)&d.h_mail, 16 * sizeof(pd_u64), hipHostMallocMapped | hipHostMallocCoherent));   // (coherent by request, not by HIP_HOST_COHERENT's default: both sides poll these words)
     memset(d.h_mail, 0, 16 * sizeof(pd_u64));
     if (hipHostGetDevicePointer((void **)&d.d_mail, d.h_mail, 0) != hipSuccess) { (void)hipGetLastError(); d.d_mail = nullptr; }
@@ -1608,18 +1593,13 @@ int pd_launch(nl_engine *e, int stream, int token, int pos, int n, float *host_l
     nl_engine::Persist &d = e->pd;
     const nl_config &c = e->cfg;
     if (d.tag_base > 0xf0000000u) {      // (tags never repeat inside the life of the areas: start over from clean ones)
-        const size_t L1 = (size_t)c.n_layers + 1;
-        HIPCK(e, hipMemsetAsync(d.gx, 0, L1 * c.dim * 8, e->stream)); HIPCK(e, hipMemsetAsync(d.go, 0, L1 * c.dim * 8, e->stream));
-        HIPCK(e, hipMemsetAsync(d.gqkv, 0, L1 * 3 * c.dim * 8, e->stream));
-        HIPCK(e, hipMemsetAsync(d.gxp, 0, L1 * c.dim * 8, e->stream)); HIPCK(e, hipMemsetAsync(d.gh, 0, L1 * (size_t)(c.interm / pd_h_vpg(c.interm)) * 16, e->stream));
-        HIPCK(e, hipMemsetAsync(d.gam, 0, (size_t)PD_GRID * 16, e->stream));
-        HIPCK(e, hipMemsetAsync(d.gpart, 0, (size_t)c.n_layers * c.n_heads * (PD_PARTS - 1) * 66 * 8, e->stream));
+        HIPCK(e, hipMemsetAsync(d.arena, 0, d.arena_bytes, e->stream));
         d.tag_base = 0;
     }
     PdParams P{};
     P.census = d.census + (d.launch_no & 1u) * 16; P.census_next = d.census + ((d.launch_no + 1u) & 1u) * 16;
     d.launch_no++;
-    P.session = session ? 1 : 0; P.idle_ticks = e->knobs.persist_idle_ticks; P.mbox = d.d_mail; P.host_done = d.d_mail ? d.d_mail + 8 : nullptr; P.gtok = d.gtok;
+    P.session = session ? 1 : 0; P.idle_ticks = e->knobs.persist_idle_ticks; P.mbox = d.d_mail; P.host_done = d.d_mail ? d.d_mail + 8 : nullptr;
     P.D = c.dim; P.I = c.interm; P.H = c.n_heads; P.V = c.vocab; P.L = c.n_layers; P.seq_len = c.seq_len; P.rope_conj = c.rope_conjugate;
     P.n_steps = n; P.token0 = token; P.pos0 = pos; P.spin_limit = e->knobs.persist_spin_limit;
     P.eps = c.rms_eps; P.scale = (float)(1.0 / std::sqrt((double)e->hd));
@@ -1633,7 +1613,7 @@ int pd_launch(nl_engine *e, int stream, int token, int pos, int n, float *host_l
     P.rope_cos = e->rope_cos; P.rope_sin = e->rope_sin;
     P.kcache = e->kcache + (long long)stream * e->kv_stream_stride; P.vcache = e->vcache + (long long)stream * e->kv_stream_stride;
     P.kv_layer_stride = e->kv_layer_stride;
-    P.gx = d.gx; P.gqkv = d.gqkv; P.go = d.go; P.gxp = d.gxp; P.gh = d.gh; P.gam = d.gam; P.gpart = d.gpart;
+    P.arena = d.arena;
     P.ids_out = e->ids; P.logits = e->logits; P.host_logits = host_logits;
     P.status = d.status; P.host_status = d.h_status; P.dbg = d.dbg;
 #define PD_LAUNCH(NB, NBI, KVH) do { \
@@ -1760,6 +1740,15 @@ int pd_session_step(nl_engine *e, int stream, int token, int pos, bool want_logi
             if (__atomic_load_n(d.h_status, __ATOMIC_ACQUIRE)) break;
             if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) break;
             __builtin_ia32_pause();
+        }
+        // A step that arrived is served only from a launch in which no poll has given up.  The dead flag is looked at once per layer
+        // slot, so a unit whose poll gave up runs on to the next check and publishes rows computed on stale granules under a valid
+        // tag: if only some units timed out the rest of the chip carries the step to its end, logits and done word included.  The
+        // give-up stores the host status word at once -- phases ahead of the done word of that step -- so it is read again here; a
+        // step with a give-up bit takes the path of a launch that ended: drained, redone on the launch plans, the path retired.
+        if (done) {
+            const unsigned st = __atomic_load_n(d.h_status, __ATOMIC_ACQUIRE);
+            if (st && !(st & 256u)) done = false;
         }
         if (!done) {       // the launch ended (idle just as the command arrived, or a poll gave up) -- or is stuck
             HIPCK(e, hipStreamSynchronize(e->stream));

@@ -33,6 +33,12 @@
 // (it then redoes the chunk on the launch plans and retires this path, like the fused plans of nl_block.h).  h -- which feeds
 // only the digit images, no sum tied to a lane layout -- travels three (I 1536) or two (I 512) values to a 16-byte granule
 // (pd_h_row, pd_publish16 / pd_gather16): a third fewer bytes and one load instead of three per lane and poll.
+// All granule areas live in ONE arena (pd_arena): a store or a poll is a raw buffer access on one resource built once per step,
+// its area and layer a scalar offset -- no kernel-argument load and no 64-bit address arithmetic in front of a publish.
+// Between a phase's barrier and the store that publishes its rows -- which 31 units poll for -- sits the row sum and nothing else:
+// the float64 tail of a norm runs under the operand latency of the products it scales (pd_inv_rms_tail, pd_units_impl's pre()),
+// a lane's unit indices are derived in front of the wait that precedes the phase (pd_units_at), and the dead flag is looked at
+// once per layer slot and once at the LM head, with the phase's operands (see the Q | K | V phase).
 // Below position 128 a head's single attention record is normalised and published by the wavefront that reduced it (no record in
 // LDS, no barrier, no merge); a chunk's logits go to device memory only on the launch's last step (every step in a session).
 //
@@ -88,6 +94,34 @@ __host__ __device__ inline void pd_unit_rc(int u, int NB, int &row, int &blk) { 
 __host__ __device__ constexpr int pd_h_vpg(int I) { return I % 96 == 0 ? 3 : I % 64 == 0 ? 2 : 0; }
 __host__ __device__ inline int pd_h_row(int idx, int lr, int I) { const int S = I / pd_h_vpg(I), SU = S / PD_CUS; return (lr / SU) * S + idx * SU + lr % SU; }
 
+// THE HAND-OFF ARENA: every granule area of a launch in ONE allocation (always sized for PD_MAXL layers, so that the kernel's
+// buffer resource has a compile-time range that IS the allocation; one pointer in PdParams, one memset, one buffer resource
+// per step in the kernel: a publish or a poll is a raw buffer access whose scalar offset is area + layer * layer_stride -- compile-time
+// constants of the instantiation -- instead of a kernel-argument load, a wait and 64-bit address arithmetic per area pointer).
+//   [0, 16)                      tok: the doorman's {tag, token} (resident session); the rest of its 128-byte line is unused
+//   [128, 128 + 256 * 16)        am: the 256 argmax granules {tag, max bits, index, -}
+//   then L + 1 layer records of layer_stride bytes (record L holds only x: the final residual stream):
+//     x [D] x 8 | qkv [3 D] x 8 | o [D] x 8 | xp [D] x 8 | h [I / VPG] x 16 | part [H][PD_PARTS - 1][66] x 8 | pad to 128
+// Every area starts on a 16-byte boundary (D and I are multiples of 32, 66 * 8 = 33 * 16).  The two areas that are written from OTHER
+// XCDs (write-through stores: am, and x of a record whose producer lives elsewhere) are whole 128-byte lines of their own, as they
+// were as separate allocations: no line mixes write-through granules with granules that stay in one XCD's L2.  The largest admitted
+// shape (D 576, I 1536, H 9, L 16) is 17 records of 45440 bytes: 777 KB, far below 2^31 -- every offset is a 32-bit value
+// (tests/host/pd_arena_check.hip walks every granule of every phase).
+struct PdArena {
+    unsigned tok, am, layers;                 // byte offsets of the two launch-wide areas and of layer record 0
+    unsigned x, qkv, o, xp, h, part;          // byte offsets inside a layer record
+    unsigned layer_stride, total;             // bytes of a record; of the whole arena
+};
+__host__ __device__ constexpr PdArena pd_arena(int D, int I, int H, int L) {
+    PdArena A{};
+    A.tok = 0; A.am = 128; A.layers = A.am + (unsigned)PD_GRID * 16u;
+    A.x = 0; A.qkv = A.x + (unsigned)D * 8u; A.o = A.qkv + 3u * (unsigned)D * 8u; A.xp = A.o + (unsigned)D * 8u; A.h = A.xp + (unsigned)D * 8u;
+    A.part = A.h + (unsigned)(I / pd_h_vpg(I)) * 16u;
+    A.layer_stride = (A.part + (unsigned)H * (unsigned)(PD_PARTS - 1) * 66u * 8u + 127u) & ~127u;
+    A.total = A.layers + (unsigned)(L + 1) * A.layer_stride;
+    return A;
+}
+
 inline bool pd_shape_ok(int D, int I, int H, int KV, int hd, int V, int L) {
     if (hd != 64 || KV < 1 || H % KV || D != H * 64 || D % 32 || I % 32 || H < 1 || H > 16 || L < 1 || L > PD_MAXL) return false;
     if (!pd_h_vpg(I)) return false;                                              // h's granules: three or two values each
@@ -125,12 +159,12 @@ struct PdParams {
     const float *rope_cos, *rope_sin;
     float *kcache, *vcache;          // layer 0 of the stream: [kv head][seq][64]
     long long kv_layer_stride;
-    pd_u64 *gx;                      // [L + 1][D]: input x of layer l >= 1; [L] = the final residual stream
-    pd_u64 *gqkv;                    // [L][3 D]: q | k | v rows of the position before RoPE (row-split over the XCD's units, read by the heads)
-    pd_u64 *go, *gxp;                // [L][D]: heads' attention outputs; x' = x + WO o
-    pd_u32x4 *gh;                    // [L][I / VPG] x 16 B: SiLU(gate) * up, {tag, h[g], h[g + S], h[g + 2 S]} (pd_h_row)
-    pd_u64 *gpart;                   // [L][H][PD_PARTS - 1][66]: a helper's merged (max, sum, sum p v[64]) of its passes, for the head's owner
-    pd_u32x4 *gam;                   // [256] {tag, max bits, index, -}
+    // the hand-off arena (pd_arena): per layer record x [D] (input x of layer l >= 1; record L = the final residual stream), qkv [3 D]
+    // (q | k | v rows of the position before RoPE: row-split over the XCD's units, read by the heads), o and xp [D] (heads' attention
+    // outputs; x' = x + WO o), h [I / VPG] x 16 B (SiLU(gate) * up, {tag, h[g], h[g + S], h[g + 2 S]}: pd_h_row), part [H][PD_PARTS - 1][66]
+    // (a helper's merged (max, sum, sum p v[64]) of its passes, for the head's owner); launch-wide am [256] {tag, max bits, index, -}
+    // and tok (the doorman's {tag, token} for the other units of its XCD)
+    pd_u32x4 *arena;
     unsigned *census, *census_next;  // [8] tickets per XCD, [8] arrivals of THIS launch; the next launch's words (zeroed here: no memset between launches)
     int *ids_out;                    // [n_steps]
     float *logits;                   // [V] of the last step
@@ -145,7 +179,6 @@ struct PdParams {
     long long idle_ticks;
     const pd_u64 *mbox;
     pd_u64 *host_done;
-    pd_u64 *gtok;                    // the doorman's {tag, token} for the other units of its XCD
 };
 
 struct PdPackParams {
@@ -267,24 +300,28 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t pd_rsrc(const void *p, unsigne
 }
 // L1-bypassing loads the compiler counts (buffer_load ... sc1): served by this XCD's L2, or by the fabric for a line a
 // write-through store dropped
-__device__ __forceinline__ pd_u64 pd_ld8(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    const pd_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, 0, 16);
+// (soff: the scalar offset of the access -- an area of the arena and the layer's record, pd_arena)
+__device__ __forceinline__ pd_u64 pd_ld8(__amdgpu_buffer_rsrc_t r, unsigned byte_off, unsigned soff = 0u) {
+    const pd_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)byte_off, (int)soff, 16);
     return ((pd_u64)v.y << 32) | v.x;
 }
-__device__ __forceinline__ pd_u32x4 pd_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 16);
+__device__ __forceinline__ pd_u32x4 pd_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off, unsigned soff = 0u) {
+    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, (int)soff, 16);
 }
 __device__ __forceinline__ float4 pd_ld16f(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
     const pd_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 16);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-// a granule for a consumer on THIS XCD stays in the XCD's L2 (workgroup-scope store: written through the L1 only); one
-// for another XCD is written through to the fabric (agent scope)
+// a granule for a consumer on THIS XCD stays in the XCD's L2 (written through the L1 only); one for another XCD is written
+// through to the fabric.  One aligned 8-byte vector store {value, tag} at byte voff of (area + record) soff of the arena, with the
+// cache-policy bits the relaxed atomic stores of the pointer form compiled to: workgroup scope = "global_store_dwordx2 ... sc0"
+// (PD_ST16_AUX, pd_publish16's form), agent scope = "global_store_dwordx2 ... sc1" (PD_ST_AUX_CROSS)
+constexpr int PD_ST16_AUX = 1;      // sc0: written through the L1 into this XCD's L2
+constexpr int PD_ST_AUX_CROSS = 16; // sc1: written through to the fabric
 template <bool CROSS>
-__device__ __forceinline__ void pd_publish(pd_u64 *p, unsigned tag, float v) {
-    const pd_u64 g = ((pd_u64)tag << 32) | __float_as_uint(v);
-    if (CROSS) __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+__device__ __forceinline__ void pd_publish(__amdgpu_buffer_rsrc_t ar, unsigned soff, unsigned voff, unsigned tag, float v) {
+    const pd_u32x2 g = {__float_as_uint(v), tag};
+    __builtin_amdgcn_raw_buffer_store_b64(g, ar, (int)voff, (int)soff, CROSS ? PD_ST_AUX_CROSS : PD_ST16_AUX);
 }
 
 struct PdPoll {
@@ -297,15 +334,14 @@ __device__ __forceinline__ void pd_give_up(const PdPoll &Q, unsigned code, int t
 }
 // n granules -> v[k] = value of granule tid + 512 k (a wavefront leaves when all of its granules carry the tag); bounded
 template <int NPT>
-__device__ __forceinline__ void pd_gather(const pd_u64 *g, int n, unsigned tag, float (&v)[NPT], const PdPoll &Q, unsigned code, int tid) {
-    const __amdgpu_buffer_rsrc_t r = pd_rsrc(g, (unsigned)n * 8u);
+__device__ __forceinline__ void pd_gather(__amdgpu_buffer_rsrc_t r, unsigned soff, int n, unsigned tag, float (&v)[NPT], const PdPoll &Q, unsigned code, int tid) {
     unsigned off[NPT];
 #pragma unroll
     for (int k = 0; k < NPT; k++) off[k] = (unsigned)min(tid + k * PD_THREADS, n - 1) * 8u;
     pd_u64 q[NPT];
     for (int spins = 0;; spins++) {
 #pragma unroll
-        for (int k = 0; k < NPT; k++) q[k] = pd_ld8(r, off[k]);
+        for (int k = 0; k < NPT; k++) q[k] = pd_ld8(r, off[k], soff);
         bool ok = true;
 #pragma unroll
         for (int k = 0; k < NPT; k++) ok &= (unsigned)(q[k] >> 32) == tag;
@@ -324,18 +360,16 @@ __device__ __forceinline__ void pd_gather(const pd_u64 *g, int n, unsigned tag, 
 
 // h: n 16-byte granules {tag, v0, v1, v2} -> v[k] of granule tid, one load per lane and poll (the form of the argmax exchange).  The
 // producer's one 16-byte store is seen whole or not at all (nl_op_gran16_soak_local).  The loop, its bound and its give-up are pd_gather's.
-constexpr int PD_ST16_AUX = 1;      // sc0: what the workgroup-scope store of pd_publish<false> compiles to (written through the L1 into this XCD's L2)
 constexpr int DPP_ROW_SHL4 = 0x104, DPP_ROW_SHL8 = 0x108;      // row_shl:n -- lane l of a row of 16 reads lane l + n (0 beyond the row)
-__device__ __forceinline__ void pd_publish16(pd_u32x4 *base, unsigned bytes, unsigned idx, unsigned tag, float v0, float v1, float v2) {
+__device__ __forceinline__ void pd_publish16(__amdgpu_buffer_rsrc_t r, unsigned soff, unsigned idx, unsigned tag, float v0, float v1, float v2) {
     const pd_u32x4 g = {tag, __float_as_uint(v0), __float_as_uint(v1), __float_as_uint(v2)};
-    __builtin_amdgcn_raw_buffer_store_b128(g, pd_rsrc(base, bytes), (int)(idx * 16u), 0, PD_ST16_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(g, r, (int)(idx * 16u), (int)soff, PD_ST16_AUX);
 }
-__device__ __forceinline__ void pd_gather16(const pd_u32x4 *g, int n, unsigned tag, float (&v)[3], const PdPoll &Q, unsigned code, int tid) {
-    const __amdgpu_buffer_rsrc_t r = pd_rsrc(g, (unsigned)n * 16u);
+__device__ __forceinline__ void pd_gather16(__amdgpu_buffer_rsrc_t r, unsigned soff, int n, unsigned tag, float (&v)[3], const PdPoll &Q, unsigned code, int tid) {
     const unsigned off = (unsigned)min(tid, n - 1) * 16u;
     pd_u32x4 q;
     for (int spins = 0;; spins++) {
-        q = pd_ld16(r, off);
+        q = pd_ld16(r, off, soff);
         if (__all(q.x == tag)) break;
         if (spins >= Q.spin_limit || ((spins & 63) == 63 && __hip_atomic_load(Q.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
             pd_give_up(Q, code, tid);
@@ -363,8 +397,9 @@ __global__ void __launch_bounds__(256) pd_gran16_soak_local_kernel(pd_u32x4 *slo
     if (pair >= (unsigned)pairs) return;
     const unsigned bytes = (unsigned)(PD_XCDS * pairs * 256) * 16u, slot = (xcd * (unsigned)pairs + pair) * 256u + threadIdx.x;
     if (!(t & 1u)) {
+        const __amdgpu_buffer_rsrc_t w = pd_rsrc(slots, bytes);
         for (unsigned g = 1; g <= iters; g++) {
-            pd_publish16(slots, bytes, slot, g, __uint_as_float(g * 2654435761u + 1u), __uint_as_float(g ^ 0x5bd1e995u), __uint_as_float(~g));
+            pd_publish16(w, 0u, slot, g, __uint_as_float(g * 2654435761u + 1u), __uint_as_float(g ^ 0x5bd1e995u), __uint_as_float(~g));
             if ((g & 7u) == 0u) __builtin_amdgcn_s_sleep(1);
         }
         return;
@@ -456,9 +491,28 @@ __device__ __forceinline__ void pd_limbs(float v, bool valid, int e, unsigned ch
 // them in float32 and multiplies by d and the block's 1 / scale -> part[row * NBP + block].  (The float32 dot product of the
 // reference, go/quant.go:149-165, has a rounding per element; this form is exact up to the 2^-30 input rounding and three
 // float32 roundings per block.)  One MFMA = 256 weights: a quarter of the instructions of the VALU form.
-template <int NU, int NB, class WF>   // NU unit slots; NB blocks per row; wf(k, lo, hi, d): the lane's 32 int8 and fp16 scale bits of slot k
-__device__ __forceinline__ void pd_units_impl(WF wf, const uint4 *img, const float *scl, int total, float *part, int tid) {
+// pre(): work of the phase that has to be finished in front of the barrier behind the units but needs none of their results (the
+// float64 tail of a norm, pd_inv_rms_tail): it runs once, behind the first pair's operand requests and in front of its products --
+// under the LDS latency the products wait for anyway, not between the row sums and the store that publishes them.
+// Where a lane's unit slots sit: the uint4 index of the unit's digit rows in the image (block * 8 + digit * 2; block = at >> 3) and the
+// index of its product in part (row * NBP + block).  They depend on the lane alone -- a division by NB among them -- so a phase
+// derives them IN FRONT of the wait that precedes it (the gather's poll loop), not between the barrier and its first LDS read.
+template <int NU> struct PdUnitAt { unsigned a[NU], p[NU]; };
+template <int NU, int NB>
+__device__ __forceinline__ PdUnitAt<NU> pd_units_at(int tid) {
     constexpr int NBP = NB | 1;
+    PdUnitAt<NU> r;
+#pragma unroll
+    for (int k = 0; k < NU; k++) {
+        const unsigned u = (unsigned)(k * PD_THREADS + tid), G = u >> 2, rgp = G / (unsigned)NB, blk = G - rgp * (unsigned)NB;
+        r.a[k] = blk * 8u + (u & 3u) * 2u;
+        r.p[k] = (rgp * 4u + (u & 3u)) * (unsigned)NBP + blk;
+        asm volatile("" : "+v"(r.a[k]), "+v"(r.p[k]));      // (finished here, not where they are used)
+    }
+    return r;
+}
+template <int NU, int NB, class WF, class PRE>   // NU unit slots; NB blocks per row; wf(k, lo, hi, d): the lane's 32 int8 and fp16 scale bits of slot k
+__device__ __forceinline__ void pd_units_impl(WF wf, const uint4 *img, const float *scl, int total, float *part, int tid, const PdUnitAt<NU> &at, PRE pre) {
     asm volatile("" : "+v"(tid));        // (addresses are derived per phase, not shared across phases and kept live)
     // Units go two at a time: the two chains of eight dependent products interleave (a 4x4x4 product has a few cycles of latency
     // its successor would otherwise wait for), their digit rows are requested together, and the scheduling fence sits between
@@ -471,7 +525,7 @@ __device__ __forceinline__ void pd_units_impl(WF wf, const uint4 *img, const flo
             const bool has2 = k0 + 1 < NU;
             const int k1 = has2 ? k0 + 1 : k0;
             const bool two = has2 && k1 * PD_THREADS < total;
-            unsigned u[2], row[2], blk[2];
+            unsigned u[2];
             uint4 a0[2], a1[2], wl[2], wh[2];
             unsigned d16[2];
             float sb[2];
@@ -479,12 +533,17 @@ __device__ __forceinline__ void pd_units_impl(WF wf, const uint4 *img, const flo
             for (int j = 0; j < 2; j++) {
                 const int k = j ? k1 : k0;
                 u[j] = (unsigned)(k * PD_THREADS + tid);
-                const unsigned G = u[j] >> 2, rgp = G / (unsigned)NB;
-                blk[j] = G - rgp * (unsigned)NB; row[j] = rgp * 4u + (u[j] & 3u);
-                const uint4 *ap = img + blk[j] * 8u + (u[j] & 3u) * 2u;
-                a0[j] = ap[0]; a1[j] = ap[1]; sb[j] = scl[blk[j]];
+                const uint4 *ap = img + at.a[k];
+                sb[j] = scl[at.a[k] >> 3];
                 wf(k, wl[j], wh[j], d16[j]);
+                a0[j] = ap[0]; a1[j] = ap[1];
             }
+            if (k0 == 0) pre();
+            // The block's 1 / scale and the unit's d are requested WITH the digit rows and are here before the first product (the LDS
+            // answers in order): left to itself the compiler moves both reads into the `u < total` branch behind the last product,
+            // one more LDS round trip in front of the store to part.  (An opaque use: no instruction.)
+            asm volatile("" : "+v"(sb[0]), "+v"(d16[0]));
+            if (has2) asm volatile("" : "+v"(sb[1]), "+v"(d16[1]));
             pd_i32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
 #define PD_MF(A, W, ACC) ACC = __builtin_amdgcn_mfma_i32_4x4x4i8((int)(A), (int)(W), ACC, 0, 0, 0)
             if (has2) {
@@ -502,20 +561,20 @@ __device__ __forceinline__ void pd_units_impl(WF wf, const uint4 *img, const flo
             }
 #undef PD_MF
             const float f0 = fmaf(fmaf(fmaf((float)acc0[3], 256.f, (float)acc0[2]), 256.f, (float)acc0[1]), 256.f, (float)acc0[0]);
-            if ((int)u[0] < total) part[row[0] * (unsigned)NBP + blk[0]] = f0 * (h2f_bits(d16[0]) * sb[0]);
+            if ((int)u[0] < total) part[at.p[k0]] = f0 * (h2f_bits(d16[0]) * sb[0]);
             if (has2) {
                 const float f1 = fmaf(fmaf(fmaf((float)acc1[3], 256.f, (float)acc1[2]), 256.f, (float)acc1[1]), 256.f, (float)acc1[0]);
-                if (two && (int)u[1] < total) part[row[1] * (unsigned)NBP + blk[1]] = f1 * (h2f_bits(d16[1]) * sb[1]);
+                if (two && (int)u[1] < total) part[at.p[k1]] = f1 * (h2f_bits(d16[1]) * sb[1]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
     }
 }
 // the layer matrices: quants in registers (slots K0 .. K0 + NU - 1 of the layer slot), scales in LDS
-template <int K0, int NU, int NB>
+template <int K0, int NU, int NB, class PRE>
 __device__ __forceinline__ void pd_units(const uint4 (&lo)[PD_UNITS], const uint4 (&hi)[PD_UNITS], const unsigned short *sc /* LDS: [9][512] of the slot */, const uint4 *img,
-                                         const float *scl, int total, float *part, int tid) {
-    pd_units_impl<NU, NB>([&](int k, uint4 &l, uint4 &h, unsigned &d) { l = lo[K0 + k]; h = hi[K0 + k]; d = sc[(K0 + k) * PD_THREADS + tid]; }, img, scl, total, part, tid);
+                                         const float *scl, int total, float *part, int tid, const PdUnitAt<NU> &at, PRE pre) {
+    pd_units_impl<NU, NB>([&](int k, uint4 &l, uint4 &h, unsigned &d) { l = lo[K0 + k]; h = hi[K0 + k]; d = sc[(K0 + k) * PD_THREADS + tid]; }, img, scl, total, part, tid, at, pre);
 }
 
 // argmax over a wavefront whose lanes hold candidates in ascending index order: the maximum on DPP, the lowest lane that holds
@@ -551,10 +610,11 @@ __device__ __forceinline__ float pd_exp(float xf) {
 }
 
 // sum of squares of a width-D vector spread two elements per thread -> 1 / rms (go/quant.go:597-607: float64 sum); every
-// compute unit adds the same partials in the same order.  Contains a workgroup barrier.  1 / sqrt(m) = v_rsq_f64 + two Newton
-// steps (relative error < 1e-30 before the float32 rounding) instead of the IEEE divide and square root: sixty dependent
-// float64 instructions shorter.
-__device__ __forceinline__ float pd_inv_rms(float a, float b, bool v0, bool v1, int lane, int wave, double *dred, int D, float eps) {
+// compute unit adds the same partials in the same order.  Two halves with the caller's workgroup barrier between them:
+// pd_sumsq leaves the wavefronts' partial sums in dred, pd_inv_rms_tail adds them and turns the mean into 1 / rms.
+// 1 / sqrt(m) = v_rsq_f64 + two Newton steps (relative error < 1e-30 before the float32 rounding) instead of the IEEE
+// square root and the divide by it: sixty dependent float64 instructions shorter.
+__device__ __forceinline__ void pd_sumsq(float a, float b, bool v0, bool v1, int lane, int wave, double *dred) {
     double ss = 0.0;
     if (v0) ss = fma((double)a, (double)a, ss);
     if (v1) ss = fma((double)b, (double)b, ss);
@@ -563,18 +623,27 @@ __device__ __forceinline__ float pd_inv_rms(float a, float b, bool v0, bool v1, 
     //  instructions of the float64 form; wavefronts are added in float64)
     const float sw = pd_rows4_sum(dpp_row_sum_f32((float)ss));
     if (lane == 0) dred[wave] = (double)sw;
-    __syncthreads();
+}
+// The tail is about thirty DEPENDENT float64 instructions (eight adds, the quotient, v_rsq_f64, two Newton steps, the conversion),
+// and only the lanes that publish a row use the result: left alone the compiler sinks the whole chain into their branch, between
+// the row sums and the publishing store every other unit of the XCD polls for.  The result is therefore made opaque where this
+// is called (every lane computes it there: pd_units_impl's pre()) -- it is a finished float32 in front of the phase's barrier.
+__device__ __forceinline__ float pd_inv_rms_tail(const double *dred, int D, float eps) {
     double t[PD_WAVES];
 #pragma unroll
     for (int w = 0; w < PD_WAVES; w++) t[w] = dred[w];
     double tot = 0.0;
 #pragma unroll
     for (int w = 0; w < PD_WAVES; w++) tot += t[w];
-    const double m = tot / (double)D + (double)eps;          // (D is a compile-time constant at the call sites: a multiply)
+    // (the IEEE float64 quotient, as written: D is a compile-time constant at the call sites but 1 / D is not exact, so this is
+    //  v_div_scale / v_rcp_f64 / four fma / v_div_fmas / v_div_fixup -- not a multiply; a reciprocal multiply would change bits)
+    const double m = tot / (double)D + (double)eps;
     double y = __builtin_amdgcn_rsq(m);
     y = y * fma(-0.5 * m * y, y, 1.5);
     y = y * fma(-0.5 * m * y, y, 1.5);
-    return (float)y;
+    float r = (float)y;
+    asm volatile("" : "+v"(r));
+    return r;
 }
 
 // a row's block products part[0 .. N) added in block order; LANES lanes share a row (q = this lane's index among them, adjacent
@@ -698,7 +767,6 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
         const int cu = (int)xcd * PD_CUS + idx;
         const int nslots = pd_nslots(L, (int)xcd), first = pd_first(L, (int)xcd);
         const bool embed_xcd = first == 0 && nslots > 0;     // this XCD owns layer 0: it turns the argmax into the next x
-        const int lm_rows = pd_lm_rows(P.V), lm_r0 = cu * lm_rows, lm_n = max(0, min(lm_rows, P.V - lm_r0));
         // ... and so are the weight registers, in place (no instruction): their int8 -> float conversions are loop-invariant and
         // would otherwise be computed once in front of the loop -- 4608 floats per lane, spilled
 #pragma unroll
@@ -733,6 +801,14 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
 #define PD_ST(base, i) do { } while (0)       // (the stamps' conditions cost scalar registers the production build does not have)
 #endif
         const unsigned tag = P.tag_base + (unsigned)step + 1u;
+        // the hand-off arena: one buffer resource per step (four scalar registers); an area of a layer's record is a scalar offset
+        constexpr PdArena AR = pd_arena(D, I, H, PD_MAXL);
+        // (its range is the arena of PD_MAXL layers, which is what the host allocates whatever L is -- a compile-time constant, like the
+        //  flags word: only the base address lives in scalar registers across the step.  The hardware checks scalar + lane offset
+        //  against it; every lane offset below is clamped to its area, and tests/host/pd_arena_check.hip walks area + record + lane
+        //  offset of every phase against the total of the model's own L)
+        const __amdgpu_buffer_rsrc_t ar = pd_rsrc(P.arena, AR.total);
+#define PD_AREA(area, layer) (AR.layers + AR.area + (unsigned)(layer) * AR.layer_stride)
         float xa = 0.f, xb = 0.f;       // this thread's two elements of the residual stream entering the next layer
         if (embed_xcd) {
             if (step > 0) {
@@ -740,10 +816,9 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 float best = -INFINITY;
                 int bidx = 0x7fffffff;
                 if (tid < PD_GRID) {
-                    const __amdgpu_buffer_rsrc_t r = pd_rsrc(P.gam, PD_GRID * 16u);
                     pd_u32x4 g;
                     for (int spins = 0;; spins++) {
-                        g = __builtin_amdgcn_raw_buffer_load_b128(r, tid * 16, 0, 16);
+                        g = pd_ld16(ar, (unsigned)tid * 16u, AR.am);
                         if (__all(g.x == tag - 1u)) break;
                         if (spins >= P.spin_limit || ((spins & 63) == 63 && __hip_atomic_load(P.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                             pd_give_up(Q, 128u, tid);
@@ -796,13 +871,12 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                         }
                         if (failed) misc[2] = 1;
                         else if (tk == 0xffffffffu) { const unsigned old = atomicOr(P.status, 256u); *P.host_status = old | 256u; misc[2] = 1; }
-                        else pd_publish<false>(P.gtok, tag, __uint_as_float(tk));
+                        else pd_publish<false>(ar, AR.tok, 0u, tag, __uint_as_float(tk));
                     }
                     if (!misc[2]) {
-                        const __amdgpu_buffer_rsrc_t r = pd_rsrc(P.gtok, 8u);
                         pd_u64 g;
                         for (int spins = 0;; spins++) {
-                            g = pd_ld8(r, 0);
+                            g = pd_ld8(ar, 0u, AR.tok);
                             if ((unsigned)(g >> 32) == tag) break;
                             if (spins >= P.spin_limit || ((spins & 63) == 63 && __hip_atomic_load(P.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                                 pd_give_up(Q, 512u, tid);
@@ -867,9 +941,10 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
             // (norm weights are requested before the polls they would otherwise wait behind)
             const float ga0 = P.norms[(size_t)(layer * 2) * D + c0], ga1 = P.norms[(size_t)(layer * 2) * D + c1];
             // ---- x of this layer (go/model.go:517): every unit of the XCD projects its rows of Q | K | V and adds residuals ----
+            const PdUnitAt<PD_UQ> at_q = pd_units_at<PD_UQ, NB>(tid);
             if (layer > 0) {
                 float xv[2];
-                pd_gather<2>(P.gx + (size_t)layer * D, D, tag, xv, Q, 1u, tid);
+                pd_gather<2>(ar, PD_AREA(x, layer), D, tag, xv, Q, 1u, tid);
                 xa = xv[0]; xb = xv[1];
             }
             if (s == 0 && idx == 0) PD_ST(sb, 1);
@@ -878,13 +953,26 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
             pd_limbs(xa * ga0, v0, e0, xl, xs, lane);
             if (wave * 64 + PD_THREADS < D) pd_limbs(xb * ga1, v1, e1, xl, xs, lane);      // (wave-uniform: the wavefronts that hold second elements)
             {
-                const float inv = pd_inv_rms(xa, xb, v0, v1, lane, wave, dred, D, P.eps);   // (its barrier also publishes the digit image)
-                if (misc[2]) return;
+                pd_sumsq(xa, xb, v0, v1, lane, wave, dred);
+                __syncthreads();                                                            // (also publishes the digit image)
                 if (s == 0 && idx == 0) PD_ST(sb, 2);
                 // ---- this unit's rows of [Q; K; V] (go/model.go:517-523): 3 D / 32 rows ----
                 float ec = 0.f, es = 0.f;      // (heads: requested before the products, the rotation below must not wait for them)
                 if (arole && tid < 128) { ec = P.rope_cos[pos * 32 + (tid & 31)]; es = P.rope_sin[pos * 32 + (tid & 31)]; }
-                pd_units<0, PD_UQ, NB>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(xl), xs, QRP * NB, part, tid);
+                // THE DEAD FLAG is looked at once per layer slot (here) and once at the LM head, and it is read with the phase's operands: a
+                // check of its own behind a barrier is an LDS round trip in front of everything the phase does, and there were five
+                // per slot.  Nothing a layer gathers is used as an address (cache rows follow pos, granules follow idx / layer), and
+                // every poll leaves within 64 spins once the status word is set: a dead launch passes at most six more polls (q | k | v,
+                // the helpers' records, o, x', h, the next x) = 384 loads per wavefront before it meets this check or the LM head's,
+                // and the host discards what it wrote (a chunk: status is read behind the launch; the resident session: pd_session_step
+                // reads the host status word again behind a step's done word, since units that did NOT time out carry a step built on
+                // a dead unit's stale rows -- published under a valid tag -- to its end).  The checks in front of the token -> embedding / gamma row lookups and in the
+                // session's mailbox path stay where they were: a garbage argmax never indexes memory.
+                float inv = 0.f;
+                int dead = 0;
+                pd_units<0, PD_UQ, NB>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(xl), xs, QRP * NB, part, tid, at_q,
+                                       [&] { dead = misc[2]; inv = pd_inv_rms_tail(dred, D, P.eps); asm volatile("" : "+v"(dead)); });
+                if (dead) return;       // (uniform: every poll since the barrier above lies behind the next one)
                 if (s == 0 && idx == 0) PD_ST(sb, 3);
                 if (arole) {  // the cache rows of the unit's first pass are requested behind the dot products (rows beyond the pass repeat
                               // its last row; the row of this position comes from LDS): they arrive during the row sums and the exchange
@@ -899,19 +987,20 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 __syncthreads();
                 PD_RELANE();
                 if (tid < 4 * QR) {       // four lanes per row; the row leaves for the head that owns it (before RoPE)
-                    const float v = pd_rowsum<NB, 4>(part + (tid >> 2) * NBP, tid & 3) * inv;
-                    if (!(tid & 3)) pd_publish<false>(P.gqkv + (size_t)layer * 3 * D + idx * QR + (tid >> 2), tag, v);
+                    const float rsum = pd_rowsum<NB, 4>(part + (tid >> 2) * NBP, tid & 3);
+                    if (s == 0 && idx == 0) PD_ST(44, 0);
+                    if (!(tid & 3)) pd_publish<false>(ar, PD_AREA(qkv, layer), (unsigned)(idx * QR + (tid >> 2)) * 8u, tag, rsum * inv);
+                    if (s == 0 && idx == 0) PD_ST(44, 1);
                 }
                 if (arole) {
                     // ---- the head's q | k | v of this position: 192 granules (a helper: q only); RoPE (go/model.go:449-477: pairs
                     //      (i, i + 32) = lanes l, l ^ 32 of a wavefront), KV store by the owner (go/model.go:552-554) ----
                     if (tid < (head ? 192 : 64)) {
                         const int sect = tid >> 6, e = tid & 63;
-                        const __amdgpu_buffer_rsrc_t r = pd_rsrc(P.gqkv + (size_t)layer * 3 * D, 3u * D * 8u);
                         const unsigned off = (unsigned)((sect == 0 ? hidx * 64 : sect == 1 ? D + (hidx / GQ) * 64 : D + KVD + (hidx / GQ) * 64) + e) * 8u;
                         pd_u64 g;
                         for (int spins = 0;; spins++) {
-                            g = pd_ld8(r, off);
+                            g = pd_ld8(ar, off, PD_AREA(qkv, layer));
                             if (__all((unsigned)(g >> 32) == tag)) break;
                             if (spins >= Q.spin_limit || ((spins & 63) == 63 && __hip_atomic_load(Q.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                                 pd_give_up(Q, 32u, tid);
@@ -935,7 +1024,6 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                     }
                     __syncthreads();
                     PD_RELANE();
-                    if (misc[2]) return;
                 // ---- softmax attention over positions 0 .. pos (go/model.go:557-587), 128 positions per pass: nl_block.h's
                     //      one-barrier pass (every wavefront reduces its 16 positions to one (max, sum, sum p v) partial) ----
                     if (s == 0 && idx == 0) PD_ST(sb, 4);
@@ -991,7 +1079,7 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                             for (int w = 0; w < 8; w++) ov = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(wgt), w)), wpart[w * 68 + 4 + lane], ov);
                             if (single) {      // the only record there is: o leaves from here -- no record in LDS, no barrier, no merge below
                                 if (s == 0 && idx == 0) PD_ST(sb, 5);
-                                pd_publish<false>(P.go + (size_t)layer * D + hidx * 64 + lane, tag, ov * (1.0f / Ls));
+                                pd_publish<false>(ar, PD_AREA(o, layer), (unsigned)(hidx * 64 + lane) * 8u, tag, ov * (1.0f / Ls));
                                 if (s == 0 && idx == 0) PD_ST(sb, 6);
                             } else {
                                 chunk[nci * 66 + 2 + lane] = ov;
@@ -1004,10 +1092,9 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                     if (head && nparts > 1) {
                         const int np1 = nparts - 1;
                         if (tid < np1 * 66) {
-                            const __amdgpu_buffer_rsrc_t r = pd_rsrc(P.gpart + ((size_t)layer * H + hidx) * (PD_PARTS - 1) * 66, (unsigned)((PD_PARTS - 1) * 66) * 8u);
                             pd_u64 g;
                             for (int spins = 0;; spins++) {
-                                g = pd_ld8(r, (unsigned)tid * 8u);
+                                g = pd_ld8(ar, (unsigned)tid * 8u, PD_AREA(part, layer) + (unsigned)hidx * (unsigned)((PD_PARTS - 1) * 66 * 8));
                                 if (__all((unsigned)(g >> 32) == tag || tid >= np1 * 66)) break;
                                 if (spins >= Q.spin_limit || ((spins & 63) == 63 && __hip_atomic_load(Q.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                                     pd_give_up(Q, 4096u, tid);
@@ -1018,10 +1105,9 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                         }
                         nci += np1;
                     }
-                    // (single: no poll has run since the check behind the q | k | v gather, and nothing below reads LDS this phase wrote)
+                    // (single: nothing below reads LDS this phase wrote)
                     if (!single) __syncthreads();
                     PD_RELANE();
-                    if (!single && misc[2]) return;
                     if (!single && s == 0 && idx == 0) PD_ST(sb, 5);
                     if (!single && tid < 64) {
                         // the records merged like position splits (fixed order: own passes from the highest down, then the helpers by part)
@@ -1035,11 +1121,11 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                                 Ls += w * chunk[c * 66 + 1];
                                 v += w * chunk[c * 66 + 2 + tid];
                             }
-                        if (head) pd_publish<false>(P.go + (size_t)layer * D + hidx * 64 + tid, tag, v * (1.0f / Ls));      // -> every unit of this XCD
+                        if (head) pd_publish<false>(ar, PD_AREA(o, layer), (unsigned)(hidx * 64 + tid) * 8u, tag, v * (1.0f / Ls));      // -> every unit of this XCD
                         else {      // a helper: its record for the owner
-                            pd_u64 *dst = P.gpart + (((size_t)layer * H + hidx) * (PD_PARTS - 1) + (apart - 1)) * 66;
-                            pd_publish<false>(dst + 2 + tid, tag, v);
-                            if (tid == 0) { pd_publish<false>(dst, tag, M); pd_publish<false>(dst + 1, tag, Ls); }
+                            const unsigned dst = PD_AREA(part, layer) + (unsigned)(hidx * (PD_PARTS - 1) + (apart - 1)) * (66u * 8u);
+                            pd_publish<false>(ar, dst, (unsigned)(2 + tid) * 8u, tag, v);
+                            if (tid == 0) { pd_publish<false>(ar, dst, 0u, tag, M); pd_publish<false>(ar, dst, 8u, tag, Ls); }
                         }
                     }
                     if (!single && s == 0 && idx == 0) PD_ST(sb, 6);
@@ -1050,29 +1136,30 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 constexpr int nr = WR, nrp = WRP, rgp = GRP;
                 const int r0 = idx * WR;
                 // ---- o of every head -> LDS; WO rows + residual (go/model.go:590-594) ----
+                const PdUnitAt<PD_UW> at_w = pd_units_at<PD_UW, NB>(tid);
                 {
                     float ov[2];
-                    pd_gather<2>(P.go + (size_t)layer * D, D, tag, ov, Q, 2u, tid);
+                    pd_gather<2>(ar, PD_AREA(o, layer), D, tag, ov, Q, 2u, tid);
                     pd_limbs(ov[0], v0, e0, xl, xs, lane);
                     if (wave * 64 + PD_THREADS < D) pd_limbs(ov[1], v1, e1, xl, xs, lane);
                 }
                 __syncthreads();
                 PD_RELANE();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 2);
-                if (misc[2]) return;
-                pd_units<PD_UQ, PD_UW, NB>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(xl), xs, nrp * NB, part, tid);
+                pd_units<PD_UQ, PD_UW, NB>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(xl), xs, nrp * NB, part, tid, at_w, [] {});
                 __syncthreads();
                 PD_RELANE();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 3);
                 if (tid < 4 * nr) {    // four lanes per row
                     const float v = pd_rowsum<NB, 4>(part + (tid >> 2) * NBP, tid & 3);
-                    if (!(tid & 3)) pd_publish<false>(P.gxp + (size_t)layer * D + r0 + (tid >> 2), tag, xraw[r0 + (tid >> 2)] + v);
+                    if (!(tid & 3)) pd_publish<false>(ar, PD_AREA(xp, layer), (unsigned)(r0 + (tid >> 2)) * 8u, tag, xraw[r0 + (tid >> 2)] + v);
                 }
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 4);
                 // ---- x' of every worker; RMSNorm; gate and up rows, SiLU(gate) * up (go/model.go:597-606) ----
                 const float gf0 = P.norms[(size_t)(layer * 2 + 1) * D + c0], gf1 = P.norms[(size_t)(layer * 2 + 1) * D + c1];
                 float xp[2];
-                pd_gather<2>(P.gxp + (size_t)layer * D, D, tag, xp, Q, 4u, tid);
+                const PdUnitAt<PD_UG> at_g = pd_units_at<PD_UG, NB>(tid);
+                pd_gather<2>(ar, PD_AREA(xp, layer), D, tag, xp, Q, 4u, tid);
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 5);
                 // (no barrier: a wavefront is here only when ALL of x' has arrived -- this unit's rows too, published by lanes that read
                 //  xraw and, through their quad, the row's block products first; the digit image of o was released by the barrier
@@ -1082,10 +1169,12 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 if (v1) xraw[e1] = xp[1];
                 pd_limbs(xp[0] * gf0, v0, e0, xl, xs, lane);
                 if (wave * 64 + PD_THREADS < D) pd_limbs(xp[1] * gf1, v1, e1, xl, xs, lane);
-                const float inv2 = pd_inv_rms(xp[0], xp[1], v0, v1, lane, wave, dred, D, P.eps);
-                if (misc[2]) return;
+                pd_sumsq(xp[0], xp[1], v0, v1, lane, wave, dred);
+                __syncthreads();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 6);
-                pd_units<PD_UQ + PD_UW, PD_UG, NB>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(xl), xs, 2 * rgp * NB, part, tid);
+                float inv2 = 0.f;
+                pd_units<PD_UQ + PD_UW, PD_UG, NB>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(xl), xs, 2 * rgp * NB, part, tid, at_g,
+                                                   [&] { inv2 = pd_inv_rms_tail(dred, D, P.eps); });
                 __syncthreads();
                 PD_RELANE();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 7);
@@ -1096,6 +1185,7 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                     const int i = min(tid >> 4, HSU - 1), k = min((tid >> 2) & 3, HVPG - 1), row = k * HSU + i, mat = (tid >> 1) & 1;
                     const float own = pd_rowsum<NB, 2>(part + (mat * rgp + row) * NBP, tid & 1) * inv2;
                     const float other = dpp_f32<DPP_QUAD_XOR2>(own);
+                    if (s == 0 && idx == 0) PD_ST(sb + 16, 12);
                     float hval = 0.f;
                     if (!(tid & 3)) {
                         const float g = own, u = other;
@@ -1104,14 +1194,15 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                     }
                     const float h1 = dpp_f32<DPP_ROW_SHL4>(hval), h2 = dpp_f32<DPP_ROW_SHL8>(hval);      // lane l: the value of lane l + 4, l + 8 of its row
                     if (!(tid & 15) && (tid >> 4) < HSU)
-                        pd_publish16(P.gh + (size_t)layer * HS, (unsigned)HS * 16u, (unsigned)(idx * HSU + (tid >> 4)), tag, hval, h1, HVPG == 3 ? h2 : 0.f);
+                        pd_publish16(ar, PD_AREA(h, layer), (unsigned)(idx * HSU + (tid >> 4)), tag, hval, h1, HVPG == 3 ? h2 : 0.f);
                 }
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 8);
                 // ---- h of every worker -> LDS; down rows + residual (go/model.go:609-612) ----
+                const PdUnitAt<PD_UD> at_d = pd_units_at<PD_UD, NBI>(tid);
                 {
                     float hv[3];
                     if (wave * 64 < HS) {      // granule tid: elements tid + k * HS, a whole block per half wavefront and k
-                        pd_gather16(P.gh + (size_t)layer * HS, HS, tag, hv, Q, 8u, tid);
+                        pd_gather16(ar, PD_AREA(h, layer), HS, tag, hv, Q, 8u, tid);
 #pragma unroll
                         for (int k = 0; k < HVPG; k++) pd_limbs(hv[k], true, tid + k * HS, hl, hs, lane);
                     }
@@ -1119,8 +1210,7 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 __syncthreads();
                 PD_RELANE();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 9);
-                if (misc[2]) return;
-                pd_units<PD_UQ + PD_UW + PD_UG, PD_UD, NBI>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(hl), hs, nrp * NBI, part, tid);
+                pd_units<PD_UQ + PD_UW + PD_UG, PD_UD, NBI>(wlo[s], whi[s], wsl + s * PD_UNITS * PD_THREADS, reinterpret_cast<const uint4 *>(hl), hs, nrp * NBI, part, tid, at_d, [] {});
                 __syncthreads();
                 PD_RELANE();
                 if (s == 0 && idx == 0) PD_ST(sb + 16, 10);
@@ -1129,8 +1219,8 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                     const float tot = pd_rowsum<NBI, 4>(part + row * NBIP, q);
                     if (q == 0) {
                         const float xo = xraw[r0 + row] + tot;
-                        pd_u64 *dst = P.gx + (size_t)(layer + 1) * D + r0 + row;
-                        if (next_here) pd_publish<false>(dst, tag, xo); else pd_publish<true>(dst, tag, xo);
+                        const unsigned dst = PD_AREA(x, layer + 1), at = (unsigned)(r0 + row) * 8u;
+                        if (next_here) pd_publish<false>(ar, dst, at, tag, xo); else pd_publish<true>(ar, dst, at, tag, xo);
                     }
                 }
             }
@@ -1143,18 +1233,24 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
         // =================================== LM head (go/model.go:616-619), every compute unit ===================================
         {
             if (idx == 0) PD_ST(40, 0);
+            const int lm_rows = pd_lm_rows(P.V), lm_r0 = cu * lm_rows, lm_n = max(0, min(lm_rows, P.V - lm_r0));
             const float go0 = P.norms[(size_t)(L * 2) * D + c0], go1 = P.norms[(size_t)(L * 2) * D + c1];
             float xv[2];
-            pd_gather<2>(P.gx + (size_t)L * D, D, tag, xv, Q, 16u, tid);
+            const PdUnitAt<PD_ULM> at_l = pd_units_at<PD_ULM, NB>(tid);
+            pd_gather<2>(ar, PD_AREA(x, L), D, tag, xv, Q, 16u, tid);
             if (idx == 0) PD_ST(40, 1);
             pd_limbs(xv[0] * go0, v0, e0, xl, xs, lane);
             if (wave * 64 + PD_THREADS < D) pd_limbs(xv[1] * go1, v1, e1, xl, xs, lane);
-            const float inv = pd_inv_rms(xv[0], xv[1], v0, v1, lane, wave, dred, D, P.eps);
-            if (misc[2]) return;
+            pd_sumsq(xv[0], xv[1], v0, v1, lane, wave, dred);
+            __syncthreads();
+            float inv = 0.f;
+            int dead = 0;   // (the dead flag travels with the phase's operands: see the Q | K | V phase)
             const int total = pd_pad4(lm_rows) * NB;
             pd_units_impl<PD_ULM, NB>([&](int k, uint4 &l, uint4 &h, unsigned &d) {
                 l = lmw[(k * 2 + 0) * PD_THREADS + tid]; h = lmw[(k * 2 + 1) * PD_THREADS + tid]; d = lms[k * PD_THREADS + tid]; },
-                reinterpret_cast<const uint4 *>(xl), xs, total, part, tid);
+                reinterpret_cast<const uint4 *>(xl), xs, total, part, tid, at_l,
+                [&] { dead = misc[2]; inv = pd_inv_rms_tail(dred, D, P.eps); asm volatile("" : "+v"(dead)); });
+            if (dead) return;
             __syncthreads();
             PD_RELANE();
             if (idx == 0) PD_ST(40, 2);
@@ -1184,19 +1280,20 @@ __global__ void __launch_bounds__(PD_THREADS, 2) pd_decode_kernel(PdParams P0) {
                 for (int w = 1; w < 4; w++)
                     if (bv[w] > best || (bv[w] == best && bi[w] < bidx)) { best = bv[w]; bidx = bi[w]; }
                 const pd_u32x4 g = {tag, __float_as_uint(best), (unsigned)bidx, 0u};
-                __builtin_amdgcn_raw_buffer_store_b128(g, pd_rsrc(P.gam, PD_GRID * 16u), cu * 16, 0, 16);     // write-through: layer 0's XCD reads it
+                __builtin_amdgcn_raw_buffer_store_b128(g, ar, cu * 16, (int)AR.am, PD_ST_AUX_CROSS);     // write-through: layer 0's XCD reads it
             }
             __syncthreads();
             PD_RELANE();
         }
         if (idx == 0) PD_ST(40, 3);
-        if (step == 0) PD_STAMP(2);
+        if (step == 0 && P.dbg && cu == 0 && tid == 0) P.dbg[2] = wall_clock64();      // (through the re-read arguments, like everything in the loop)
     }
     if (P0.dbg && cu == 0 && tid0 == 0) P0.dbg[3] = wall_clock64();
 #undef PD_STAMP
 #undef PD_ST
 #undef PD_RELANE
 #undef PD_ACK_HOST_ROWS
+#undef PD_AREA
 }
 
 }  // namespace nl

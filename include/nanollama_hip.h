@@ -127,6 +127,22 @@ NL_API const char *nl_last_error(nl_handle h); /* h may be NULL: last create err
  * [0, mark) written since the last reset) and drops it here.  A later step at pos > mark is legal, as in the
  * reference, and sees what the reference sees: the rows [mark, pos) are cleared to zero just before that step. */
 NL_API int nl_reset(nl_handle h, int stream);
+/* KVCache.prefill (nanollama/engine.py:139-153): several samples of one prompt prefill once and copy the cache into every
+ * sample's row.  For every layer and kv head the K and V rows [0, n_pos) of stream `src` are copied into each of the n_dst
+ * streams listed in dst, in ONE launch (the source is read once).  Afterwards every destination behaves as a stream that was
+ * reset and then wrote exactly those positions itself: its high-water mark is n_pos whatever it was before, and a later step
+ * that jumps over [n_pos, pos) sees zeros there, as after nl_reset.  n_pos == 0 is nl_reset of every destination.  `src` is not
+ * touched.  Voice bindings (nl_stream_voice) are not touched either: the destinations keep the voices they were bound to, and
+ * rows computed under src's voice now sit in them -- a caller that wants the continuation in the same voice binds them itself.
+ * Errors, all found before any device work is queued, leaving every mark and every byte as it was: NL_ERR_STATE before
+ * nl_finalize; NL_ERR_INVALID for src or a destination out of range, a destination equal to src or listed twice, dst NULL,
+ * n_dst < 1 or > max_streams - 1, n_pos < 0 or > seq_len, or n_pos above src's high-water mark (rows past the mark are
+ * undefined until a step clears them).  nl_last_error names the offending value.
+ * Ordering: the call ends a resident persistent-decode session like every entry point that is not its next step, queues the
+ * copy on the engine's stream -- behind everything queued before it, in front of every later step -- and returns NL_OK without
+ * waiting for it, as nl_reset returns.  It rebuilds no plan and no graph.  On a group handle the call reaches every rank (each
+ * copies its own kv-head shard); the arguments are checked once, before any rank is touched. */
+NL_API int nl_kv_fork(nl_handle h, int src, const int *dst, int n_dst, int n_pos);
 
 /* == Forward (go/model.go:490-620) ======================================== */
 /* One token through all layers at position pos of KV stream `stream`;

@@ -137,6 +137,25 @@ func (m *LlamaModel) resetHIP() {
 	m.State.Pos = 0
 }
 
+// kvForkHIP is KVCache.prefill of the reference's Python engine (nanollama/engine.py:139-153) for a host that decodes several
+// samples of one prompt: the K / V rows [0, nPos) of stream src become the rows of every stream in dsts (nl_kv_fork: one
+// launch, queued behind the prefill, no wait).  The Go host has one stream per process (max_streams 1 in loadHIP, go/main.go
+// generates one completion), so nothing here calls it; a host that sets max_streams = N and steps the N rows through
+// nl_forward_batch_sample forks after its nl_prefill.  Voice bindings are left alone (nl_stream_voice).
+func (m *LlamaModel) kvForkHIP(src int, dsts []int, nPos int) error {
+	if len(dsts) == 0 {
+		return fmt.Errorf("nl_kv_fork: no destination stream")
+	}
+	ids := make([]C.int, len(dsts))
+	for i, d := range dsts {
+		ids[i] = C.int(d)
+	}
+	if rc := C.nl_kv_fork(m.hip.h, C.int(src), &ids[0], C.int(len(ids)), C.int(nPos)); rc != 0 {
+		return hipErr(m.hip.h, rc, "nl_kv_fork")
+	}
+	return nil
+}
+
 // applyGammaHIP hands the gamma essence (go/gamma.go, go/main.go:70-83) to the device: Forward adds
 // gamma[token] to the embedding row there (go/model.go:503-505).
 // This is voice 0 of the handle.  Further essences on the same weights go in through nl_set_voice(h, v, ...) with the same

@@ -14,3 +14,4 @@ func loadHIP(gguf *GGUFFile, cfg *LlamaConfig, device int, gpus int) (*hipBacken
 func (b *hipBackend) logits(vocab int) []float32                                { return nil }
 func (m *LlamaModel) forwardHIP(token, pos int)                                 {}
 func (m *LlamaModel) resetHIP()                                                 {}
+func (m *LlamaModel) kvForkHIP(src int, dsts []int, nPos int) error             { return nil }

@@ -93,7 +93,8 @@ EXPORTS = ["nl_build_info", "nl_set_gamma", "nl_abi_version", "nl_device_count",
            "nl_comm_init", "nl_group_forward", "nl_debug_stamps", "nl_sample_decode", "nl_op_sample", "nl_p2p_export",
            "nl_p2p_import", "nl_p2p_info", "nl_p2p_loopback", "nl_op_exp", "nl_plan_info", "nl_persist_info", "nl_create_group", "nl_host_logits",
            "nl_op_gran16_soak", "nl_op_gran16_soak_local", "nl_forward_batch_sample", "nl_op_sample_rows", "nl_forward_mixed", "nl_forward_mixed_sample",
-           "nl_mixed_capacity", "nl_score", "nl_op_score_rows", "nl_set_voice", "nl_stream_voice", "nl_voice_info"]
+           "nl_mixed_capacity", "nl_score", "nl_op_score_rows", "nl_set_voice", "nl_stream_voice", "nl_voice_info",
+           "nl_kv_fork"]
 
 
 def lib():
@@ -118,6 +119,7 @@ def lib():
     L.nl_last_error.restype = C.c_char_p
     L.nl_last_error.argtypes = [vp]
     L.nl_reset.argtypes = [vp, i32]
+    L.nl_kv_fork.argtypes = [vp, i32, ip, i32, i32]
     L.nl_forward.argtypes = [vp, i32, i32, i32, fp]
     L.nl_forward_argmax.argtypes = [vp, i32, i32, i32, ip]
     L.nl_decode_greedy.argtypes = [vp, i32, i32, i32, i32, ip, ip]

@@ -27,6 +27,16 @@ rep_penalty and rep_window are the server's.  A request may name one of the mode
 the stream it gives the request -- or the score job -- to that voice (nl_stream_voice; none named: voice 0) before the first
 step that carries the stream's rows, so the rows of one step each take their own voice's gamma.  Each request samples from its own generator, seeded from the scheduler's
 (seeded by --seed) in admission order, and draws a uniform only while its temperature is > 0, as Engine does.
+
+Several samples of one prompt (generate_samples, "n" in POST /chat; Engine.generate(tokens, num_samples=N) and
+KVCache.prefill, nanollama/engine.py:222-299 and :139-153): the request waits at the head of the queue until n streams are
+free, its first stream -- the leader -- is reset, bound and prefilled exactly as a single request's, then ONE
+kv_fork(leader, siblings, n_prompt - 1) (nl_kv_fork) copies the prompt's K / V rows into the other n - 1 streams and all n rows
+feed the final prompt token at position n_prompt - 1, each with its own generator (the leader's drawn first, so it is the one
+an n = 1 request would have had), repetition window and text.  With prefill_chunk > 0 the leader is chunked as any request
+and the fork follows the step that fed its last chunk; the siblings join the next step.  Rows finish independently, a
+finished row's stream is free at once, and the request returns when its last row has finished.  n = 1 makes the engine calls
+a request made before there was an n.
 """
 from __future__ import annotations
 
@@ -63,6 +73,9 @@ class _Request:
     done: threading.Event = field(default_factory=threading.Event)
     text: str = ""
     error: Optional[RequestError] = None
+    n: int = 1                                       # samples: rows of the batch that share this prompt
+    texts: List[str] = field(default_factory=list)   # one per sample, in sample order
+    left: int = 0                                    # rows that have not finished yet
 
 
 @dataclass
@@ -87,6 +100,8 @@ class _Row:
     n_out: int = 0           # ids sampled so far (EOS included)
     pre: int = 0             # prefill_chunk > 0: prompt tokens (0 .. n_prompt - 2) to feed before the row decodes ...
     fed: int = 0             # ... and how many of them have been fed
+    sample: int = 0          # which of the request's n samples this row is (0: the leader, which runs the prompt)
+    siblings: List["_Row"] = field(default_factory=list)   # the leader, prefill_chunk > 0: rows that join once it forks
 
 
 class BatchScheduler:
@@ -136,11 +151,18 @@ class BatchScheduler:
     def generate_quiet(self, prompt: str, params: GenParams, voice: int = 0) -> str:
         """GenerateQuiet (go/main.go:233-291) as one row of the shared batch, in the voice with id `voice` (model.voices; 0: the
         default); blocks until the request is done.  Raises RequestError (status 400 / 500)."""
+        return self.generate_samples(prompt, params, 1, voice=voice)[0]
+
+    def generate_samples(self, prompt: str, params: GenParams, n, voice: int = 0) -> List[str]:
+        """n completions of one prompt (Engine.generate_batch, nanollama/engine.py:354) as n rows of the shared batch that
+        share one prefill; 1 <= n <= parallel.  Blocks until the last row is done; the texts come in sample order."""
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= self.parallel:
+            raise RequestError(400, f"n must be an integer in [1, {self.parallel}] (the server's --parallel), got {n!r}")
         if not params.top_p > 0:
             raise RequestError(400, f"top_p must be > 0, got {params.top_p}")
         if params.temperature > 0 and params.top_p >= 1.0 and not 1 <= params.top_k <= MAX_TOP_K:
             raise RequestError(400, f"top_k must be in [1, {MAX_TOP_K}] for batched sampling, got {params.top_k}")
-        req = _Request(self.tokenizer.encode(prompt, True), params, self._check_voice(voice))
+        req = _Request(self.tokenizer.encode(prompt, True), params, self._check_voice(voice), n=n, texts=[""] * n, left=n)
         with self._cv:
             if self._closed:
                 raise RequestError(500, "scheduler closed")
@@ -149,7 +171,7 @@ class BatchScheduler:
         req.done.wait()
         if req.error is not None:
             raise req.error
-        return req.text
+        return list(req.texts)
 
     def score(self, ids: List[int], n_context: int = 1, voice: int = 0) -> ScoreResult:
         """score.score_ids(model, ids, a free stream, n_context) on the worker, in voice `voice`; blocks until done.
@@ -173,9 +195,13 @@ class BatchScheduler:
 
     # ---- the worker ----
     def _finish(self, row: _Row, free: List[int]) -> None:
-        row.req.text = row.out.text()
+        req = row.req
+        req.texts[row.sample] = row.out.text()
         free.append(row.stream)
-        row.req.done.set()
+        req.left -= 1
+        if req.left == 0:                               # the request completes with its last row
+            req.text = req.texts[0]
+            req.done.set()
 
     def _fail(self, req, status: int, exc: BaseException) -> None:
         req.error = RequestError(status, f"{type(exc).__name__}: {exc}")
@@ -193,30 +219,49 @@ class BatchScheduler:
         free.append(stream)
         job.done.set()
 
-    def _admit(self, req: _Request, stream: int, active: List[_Row], free: List[int]) -> None:
+    def _fork(self, row: _Row, n_pos: int) -> None:
+        """The leader's rows [0, n_pos) into every sibling's stream, in one call; the siblings speak in the request's voice."""
+        self.model.kv_fork(row.stream, [s.stream for s in row.siblings], n_pos)
+        for s in row.siblings:
+            self._bind(s.stream, row.req.voice)
+
+    def _admit(self, req: _Request, streams: List[int], active: List[_Row], free: List[int]) -> None:
+        """streams: one per sample; the first is the leader's, which runs the prompt."""
+        stream = streams[0]
         if isinstance(req, _ScoreJob):
             self._score(req, stream, free)
             return
         cfg = self.model.config
         p = req.params
-        rng = np.random.default_rng(int(self.rng.integers(0, 2 ** 63 - 1)))
         n_prompt = min(len(req.tokens), max(cfg.seq_len - 1, 0))
-        row = _Row(req, stream, req.tokens[n_prompt - 1] if n_prompt else 0, n_prompt - 1, rng, TextOutput(self.tokenizer))
+        # one generator per sample, the leader's first: with one --seed it is the generator an n = 1 request would have had
+        rows = [_Row(req, s, req.tokens[n_prompt - 1] if n_prompt else 0, n_prompt - 1,
+                     np.random.default_rng(int(self.rng.integers(0, 2 ** 63 - 1))), TextOutput(self.tokenizer), sample=i)
+                for i, s in enumerate(streams)]
+        row = rows[0]
+        row.siblings = rows[1:]
         if p.max_tokens <= 0 or n_prompt <= 0:       # nothing to sample
-            self._finish(row, free)
+            for r in rows:
+                self._finish(r, free)
             return
+        fork_now = bool(row.siblings) and (not self.prefill_chunk or n_prompt == 1)
         try:
             self.model.reset(stream)
             self._bind(stream, req.voice)
             if n_prompt > 1 and not self.prefill_chunk:
                 self.model.prefill(req.tokens[:n_prompt - 1], pos0=0, stream=stream, want_logits=False)
+            if fork_now:
+                self._fork(row, n_prompt - 1)
         except Exception as exc:                        # engine error: this request fails, the scheduler goes on
-            free.append(stream)
+            free.extend(streams)
             self._fail(req, 500, exc)
             return
         if self.prefill_chunk:
             row.pre = n_prompt - 1
         active.append(row)
+        if fork_now:                                    # (chunked prompts: the siblings join behind the leader's last chunk)
+            active.extend(row.siblings)
+            row.siblings = []
 
     def _note_step(self, decoding: bool) -> None:
         """max_step_gap_ms: called when a step returns; `decoding`: it carried a row of a request that was already decoding."""
@@ -274,7 +319,7 @@ class BatchScheduler:
             failed = {id(r) for r in out_rows + touched}
             for r in active:
                 if id(r) in failed:
-                    free.append(r.stream)
+                    free.extend([r.stream] + [s.stream for s in r.siblings])
                     self._fail(r.req, 500, exc)
             active[:] = [r for r in active if id(r) not in failed]
             self._last_decode_step = None
@@ -283,9 +328,21 @@ class BatchScheduler:
         self._note_step(bool(decoding))
         for r, p0, k in chunks:
             r.fed = p0 + k
-        kept = {id(r) for r in self._apply(out_rows, ids, recents, free)}
+        joined, lost = [], set()
+        for r in out_rows:                              # a leader whose last chunk this step fed: its rows [0, pre) exist now
+            if r.siblings:
+                try:
+                    self._fork(r, r.pre)
+                    joined.extend(r.siblings)
+                except Exception as exc:                # engine error: the request fails with all its streams, as a prefill's
+                    free.extend([r.stream] + [s.stream for s in r.siblings])
+                    self._fail(r.req, 500, exc)
+                    lost.add(id(r))
+                r.siblings = []
+        going = [(r, t, rec) for r, t, rec in zip(out_rows, ids, recents) if id(r) not in lost]
+        kept = {id(r) for r in self._apply([g[0] for g in going], [g[1] for g in going], [g[2] for g in going], free)}
         sampled = {id(r) for r in out_rows}
-        active[:] = [r for r in active if id(r) in kept or id(r) not in sampled]
+        active[:] = [r for r in active if id(r) in kept or id(r) not in sampled] + joined
 
     def _step(self, active: List[_Row], free: List[int]) -> None:
         params, uniforms = self._settings(active)
@@ -315,11 +372,12 @@ class BatchScheduler:
                     pending = list(self._queue) + [r.req for r in active]
                     self._queue.clear()
                     break
-                admit = []
-                while self._queue and free:
-                    admit.append((self._queue.popleft(), free.pop(0)))
-            for req, stream in admit:
-                self._admit(req, stream, active, free)
+                admit = []                              # first in, first out: the head waits for all its streams, nothing overtakes it
+                while self._queue and len(free) >= getattr(self._queue[0], "n", 1):
+                    req = self._queue.popleft()
+                    admit.append((req, [free.pop(0) for _ in range(getattr(req, "n", 1))]))
+            for req, streams in admit:
+                self._admit(req, streams, active, free)
             if active and self.prefill_chunk:
                 self._step_mixed(active, free)
             elif active:

@@ -8,6 +8,7 @@
     python -m nanollama_amd --model m.gguf --voice leo=leo.npz --voice yent=yent.npz --serve --parallel 16
                                                                         (one base, several gamma essences: "voice" per request)
     python -m nanollama_amd --model m.gguf --voice leo=leo.npz --use-voice leo --prompt "Hello"
+    python -m nanollama_amd --model m.gguf --prompt "Hello" --samples 4 --seed 1    (four completions from one prefill)
 """
 from __future__ import annotations
 
@@ -57,7 +58,45 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--score", default="", metavar="PATH",
                     help="score the text in PATH ('-': stdin) instead of generating: prints tokens, nll, ppl, bits per byte "
                          "and tokens/s; not with --serve, --interactive or --prompt")
+    ap.add_argument("--samples", type=int, default=1, metavar="N",
+                    help="with --prompt: N completions of the prompt from ONE prefill (the prompt's K/V rows are copied into "
+                         "N - 1 further streams and the N rows decode as one batch; N <= 64), each printed under a line "
+                         "'--- sample i ---'; 1 = one completion, streamed as it is generated")
     return ap
+
+
+def check_samples(args) -> None:
+    """--samples N: N > 1 is a mode of --prompt on one GPU (the rows decode through the batched sampler)."""
+    if not 1 <= args.samples <= 64:
+        raise RuntimeError("--samples must be in [1, 64]")
+    if args.samples == 1:
+        return
+    for flag, on in (("--interactive", args.interactive), ("--score", bool(args.score)), ("--serve", args.serve)):
+        if on:
+            raise RuntimeError(f"--samples cannot be combined with {flag}" + (': a request asks with "n"' if flag == "--serve" else ""))
+    if not args.prompt:
+        raise RuntimeError("--samples needs --prompt")
+    if args.gpus > 1:
+        raise RuntimeError("--samples > 1 needs --gpus 1")
+    if not 0 <= args.rep_window <= 1024:
+        raise RuntimeError("--samples > 1 needs --rep-window <= 1024")
+
+
+def run_samples(eng, prompt: str, params: GenParams, args, out=None) -> None:
+    """--samples N: the prompt as one n = N request of a BatchScheduler of N rows; the completions in sample order."""
+    from .batch_serve import BatchScheduler, RequestError
+    out = out or sys.stdout
+    sched = BatchScheduler(eng.model, eng.tokenizer, args.samples, rep_penalty=args.rep_penalty, rep_window=args.rep_window,
+                           seed=args.seed)
+    try:
+        texts = sched.generate_samples(prompt, params, args.samples, voice=eng.model.voices[args.use_voice] if args.use_voice else 0)
+    except RequestError as exc:
+        raise RuntimeError(str(exc)) from exc
+    finally:
+        sched.close()
+    for i, text in enumerate(texts):
+        print(f"--- sample {i} ---", file=out)
+        print(text, file=out)
 
 
 def check_score(args) -> None:
@@ -185,9 +224,12 @@ def load_engine(args) -> TextEngine:
         print(f"[nanollama] tensor-parallel over devices {devs} (push all-reduce between the ranks of this process)")
         model = load_llama_model(g, devices=devs, verbose=True)
     else:
-        model = load_llama_model(g, device=args.device, max_streams=args.parallel if batched(args) else 1, verbose=True)
+        model = load_llama_model(g, device=args.device, max_streams=args.parallel if batched(args) else max(getattr(args, "samples", 1), 1),
+                                 verbose=True)
     if batched(args) and model.config.vocab_size > 131072:
         raise RuntimeError(f"--parallel > 1 covers vocabularies up to 131072, not {model.config.vocab_size}")
+    if getattr(args, "samples", 1) > 1 and model.config.vocab_size > 131072:
+        raise RuntimeError(f"--samples > 1 covers vocabularies up to 131072, not {model.config.vocab_size}")
     if args.gamma:
         from .gamma import load_gamma
         try:
@@ -247,6 +289,7 @@ def main(argv=None) -> int:
         check_parallel(args)
         check_prefill_chunk(args)
         check_score(args)
+        check_samples(args)
         check_voices(args)
         eng = load_engine(args)
         if args.prefill_chunk > 0:
@@ -278,6 +321,12 @@ def main(argv=None) -> int:
         run_server(eng, params, args.port)
     elif args.interactive:
         run_repl(eng, params)
+    elif args.prompt and args.samples > 1:
+        try:
+            run_samples(eng, args.prompt, params, args)
+        except RuntimeError as exc:
+            print(f"error: {exc}", file=sys.stderr)
+            return 1
     elif args.prompt:
         print(eng.generate(args.prompt, params, stream=sys.stdout))
     else:

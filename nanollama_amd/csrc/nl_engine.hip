@@ -16,6 +16,7 @@
 #include "nl_batch.h"
 #include "nl_sample.h"
 #include "nl_score.h"
+#include "nl_fork.h"
 #include "nl_p2p.h"
 #include "nl_block.h"
 #include "nl_group.h"
@@ -94,6 +95,7 @@ namespace {
 //   NL_PERSIST_SESSION            1           handle   0: per-call Forward is one launch per step, no resident session
 //   NL_PERSIST_IDLE_US            2000        handle   microseconds a resident session waits for the next token (1 .. 2e6)
 //   NL_PERSIST_FAKE_CENSUS_MISS   0           handle   test: the first n persistent launches count as placement misses
+//   NL_FORK_POLICY                1           handle   nl_kv_fork's cache policy: 0 = plain, 1 = non-temporal stores, 2 = loads too
 //   NL_P2P_CACHED                 unset       handle   set: cached push all-reduce receive area (ranks on ONE device only)
 //   NL_P2P_TIMEOUT_MS             10000       handle   push all-reduce: how long a poll waits for a peer
 //   NL_PREFILL_PRECISION          hi + lo     step     fp16x1: long-prompt GEMMs and prompt attention multiply the fp16 hi half
@@ -144,6 +146,7 @@ struct HandleKnobs {
     std::optional<int> tp_pair = knob_opt("NL_TP_PAIR"), tp_ct = knob_opt("NL_TP_CT");
     bool persist = !knob_off("NL_PERSIST"), persist_session = knob_int("NL_PERSIST_SESSION", 1) != 0, p2p_cached = knob_set("NL_P2P_CACHED");
     int persist_max_pos = std::max(0, std::min(PD_MAX_POS, knob_int("NL_PERSIST_MAX_POS", PD_MAX_POS))), p2p_timeout_ms = knob_int("NL_P2P_TIMEOUT_MS", 10000);
+    int fork_policy = knob_int("NL_FORK_POLICY", 1);
     int persist_spin_limit = knob_int("NL_PERSIST_SPIN_LIMIT", 2000000), persist_fake_misses = knob_int("NL_PERSIST_FAKE_CENSUS_MISS", 0);
     long long persist_idle_ticks = std::max(1LL, std::min(2000000LL, knob_ll("NL_PERSIST_IDLE_US", 2000))) * 100;   // 100 MHz clock
 };
@@ -3549,6 +3552,65 @@ int nl_reset(nl_handle e, int stream) {
     // rows a later step could read without having rewritten them are cleared then (note_positions).
     e->hw[stream] = 0;
     return NL_OK;
+}
+
+// KVCache.prefill (nanollama/engine.py:139-153): the rows [0, n_pos) of `src` become the rows of every stream in dst.
+// The argument checks, on the engine whose marks count (a group: rank 0 for the leader); nothing is queued or changed before
+// they all pass.
+namespace {
+int kv_fork_check(nl_engine *who, const nl_engine *e, int src, const int *dst, int n_dst, int n_pos) {
+    const int S = e->cfg.max_streams;
+    if (!e->finalized) return who->fail(NL_ERR_STATE, "nl_kv_fork before nl_finalize");
+    if (src < 0 || src >= S) return who->fail(NL_ERR_INVALID, "nl_kv_fork: source stream %d out of range [0,%d)", src, S);
+    if (n_dst < 1 || n_dst > S - 1) return who->fail(NL_ERR_INVALID, "nl_kv_fork: n_dst %d out of range [1,%d] (max_streams - 1)", n_dst, S - 1);
+    if (!dst) return who->fail(NL_ERR_INVALID, "nl_kv_fork: dst is null");
+    if (n_dst > FORK_MAX_DST) return who->fail(NL_ERR_INVALID, "nl_kv_fork: n_dst %d above %d", n_dst, FORK_MAX_DST);
+    for (int i = 0; i < n_dst; i++) {
+        if (dst[i] < 0 || dst[i] >= S) return who->fail(NL_ERR_INVALID, "nl_kv_fork: destination stream %d out of range [0,%d)", dst[i], S);
+        if (dst[i] == src) return who->fail(NL_ERR_INVALID, "nl_kv_fork: destination %d is the source stream", dst[i]);
+        for (int j = 0; j < i; j++)
+            if (dst[j] == dst[i]) return who->fail(NL_ERR_INVALID, "nl_kv_fork: destination stream %d listed twice", dst[i]);
+    }
+    if (n_pos < 0 || n_pos > e->cfg.seq_len) return who->fail(NL_ERR_INVALID, "nl_kv_fork: n_pos %d out of range [0,%d]", n_pos, e->cfg.seq_len);
+    if (n_pos > e->hw[src])
+        return who->fail(NL_ERR_INVALID, "nl_kv_fork: n_pos %d above the %d positions stream %d has written since its reset", n_pos, e->hw[src], src);
+    return NL_OK;
+}
+
+// one engine, arguments checked: end a resident session, queue the one launch on the engine's stream, move the marks
+int kv_fork_queue(nl_engine *e, int src, const int *dst, int n_dst, int n_pos) {
+    HIPCK(e, hipSetDevice(e->dev));
+    if (int qrc = pd_session_close(e)) return qrc;
+    if (n_pos > 0) {
+        KvForkParams P{};
+        P.kcache = e->kcache; P.vcache = e->vcache; P.kv_stream_stride = e->kv_stream_stride;
+        P.run16 = n_pos * e->hd / 4; P.pitch16 = e->cfg.seq_len * e->hd / 4;
+        P.src = src; P.n_dst = n_dst;
+        for (int i = 0; i < n_dst; i++) P.dst[i] = dst[i];
+        HIPCK(e, launch_kv_fork(P, e->cfg.n_layers * e->KVs, e->knobs.fork_policy, e->stream));
+    }
+    // a destination is a stream that was reset and wrote exactly [0, n_pos): note_positions clears what a later jump skips
+    for (int i = 0; i < n_dst; i++) e->hw[dst[i]] = n_pos;
+    return NL_OK;
+}
+}  // namespace
+
+int nl_kv_fork(nl_handle e, int src, const int *dst, int n_dst, int n_pos) {
+    if (!e) return NL_ERR_INVALID;
+    if (e->grp) {
+        if (e->grp->members.empty()) return NL_ERR_INVALID;
+        if (int rc = kv_fork_check(e, e->grp->members[0], src, dst, n_dst, n_pos)) return rc;
+        // one rank after the other (every rank copies its own kv-head shard on its own stream); no rank is stepping meanwhile
+        std::lock_guard<std::mutex> setup(g_setup_mu);
+        for (size_t r = 0; r < e->grp->members.size(); r++)
+            if (int rc = kv_fork_queue(e->grp->members[r], src, dst, n_dst, n_pos)) {
+                e->err = "rank " + std::to_string(r) + ": " + e->grp->members[r]->err;
+                return rc;
+            }
+        return NL_OK;
+    }
+    if (int rc = kv_fork_check(e, e, src, dst, n_dst, n_pos)) return rc;
+    return kv_fork_queue(e, src, dst, n_dst, n_pos);
 }
 
 float *nl_host_logits(nl_handle e) {

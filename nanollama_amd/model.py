@@ -249,6 +249,13 @@ class LlamaModel:
         _lib.check(self._h, _lib.lib().nl_reset(self._h, stream))
         self.state.pos = 0
 
+    def kv_fork(self, src: int, dsts: List[int], n_pos: int) -> None:
+        """nl_kv_fork (KVCache.prefill, nanollama/engine.py:139-153): the K / V rows [0, n_pos) of stream `src` become the
+        rows of every stream in `dsts`, which then stand at n_pos as if they had been reset and written those positions
+        themselves.  One launch, queued behind the engine's earlier work; voice bindings stay as they are."""
+        d = [int(x) for x in dsts]
+        _lib.check(self._h, _lib.lib().nl_kv_fork(self._h, int(src), (C.c_int * len(d))(*d) if d else None, len(d), int(n_pos)))
+
     # --- measurement / introspection ---
     def synchronize(self):
         _lib.check(self._h, _lib.lib().nl_synchronize(self._h))

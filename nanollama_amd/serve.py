@@ -2,13 +2,15 @@
 
     GET  /        chat UI (a minimal page of our own; the reference embeds go/ui.html)
     POST /chat    {"messages":[{"role","content"}], "temperature", "max_tokens", "top_k"} -> {"response"}
+                  (+ "n": 2 .. --parallel, with --parallel N: that many samples of the prompt from one prefill ->
+                  {"response": sample 0, "responses": [all n]}; absent or 1: the reply above; anything else 400 {"error"})
     POST /score   {"text"} or {"prompt","continuation"} (+ "details": true) -> {"tokens","logprob","nll","ppl","bpb"}
                   (+ "token_logprobs"); no counterpart in go/serve.go -- the quantity is nanollama/core_eval.py's bits per byte
                   Both bodies take an optional "voice": NAME (one of the server's --voice names; absent: the default voice,
                   --gamma or none); an unknown name is 400 {"error"}
     GET  /health  {"status","params_millions","layers","dim","heads","kv_heads","vocab_size","gamma_loaded"}
                   (+ "voices": [names] when the server has --voice entries)
-                  (+ "steps","prefill_chunk","max_step_gap_ms" with --parallel N)
+                  (+ "steps","prefill_chunk","max_step_gap_ms","max_samples" with --parallel N)
 
 One generation at a time (the model handle is single-caller): a lock around GenerateQuiet, as go/serve.go:56,106-108.
 With --parallel N the engine is a BatchScheduler (batch_serve.py): concurrent requests decode as one batch, no lock.
@@ -62,6 +64,20 @@ def bind_voice(engine, voice: int) -> None:
         engine.model.stream_voice(0, voice)
 
 
+def request_samples(engine, req: dict) -> int:
+    """The number of samples a /chat body asks for: "n", an integer in [1, parallel]; absent: 1.  Raises RequestError (400,
+    JSON) for anything else; the serial server serves n = 1 only."""
+    n = req.get("n")
+    if n is None:
+        return 1
+    most = engine.parallel if isinstance(engine, BatchScheduler) else 1
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise RequestError(400, f'"n" must be an integer >= 1, got {n!r}')
+    if n > most:
+        raise RequestError(400, f'"n" = {n} exceeds the {most} samples this server draws at once: start it with --parallel {n} or more')
+    return n
+
+
 def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
     """POST /chat (go/serve.go:69-111).  Returns (status, payload)."""
     try:
@@ -72,6 +88,7 @@ def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
         return 400, "bad request: " + str(exc)
     try:
         voice = request_voice(engine, req)
+        n = request_samples(engine, req)
     except RequestError as exc:
         return exc.status, {"error": str(exc)}
     messages = req.get("messages") or []
@@ -90,6 +107,9 @@ def handle_chat(engine, defaults: GenParams, lock: threading.Lock, body: bytes):
         params = replace(params, top_k=int(req["top_k"]))
     try:
         with lock:
+            if isinstance(engine, BatchScheduler) and n > 1:
+                results = engine.generate_samples(prompt, params, n, voice=voice)
+                return 200, {"response": results[0], "responses": results}
             if isinstance(engine, BatchScheduler):
                 result = engine.generate_quiet(prompt, params, voice=voice)
             else:
@@ -156,7 +176,8 @@ def handle_health(engine):
     if _voices(engine):                          # a server with --voice entries: their names (none: the reference's keys, no more)
         out["voices"] = list(_voices(engine))
     if isinstance(engine, BatchScheduler):       # --parallel N: the scheduler's counters (tools/bench_serve_parallel.py)
-        out.update(steps=engine.steps, prefill_chunk=engine.prefill_chunk, max_step_gap_ms=round(engine.max_step_gap_ms, 3))
+        out.update(steps=engine.steps, prefill_chunk=engine.prefill_chunk, max_step_gap_ms=round(engine.max_step_gap_ms, 3),
+                   max_samples=engine.parallel)
     return out
 
 

@@ -1481,19 +1481,36 @@ int p2p_check(nl_engine *e) {
 // cleared, the fused plan is retired for this handle, and the caller redoes its whole call on the general plan (every
 // buffer a step writes -- residual stream, K/V rows of its positions, logits, ids -- is rewritten by the redo).
 // nl_last_error carries a one-time note while the call returns NL_OK.
+// (the retirement of ONE engine, queued on st; the caller synchronises st, tears down and reports: nl_group_forward does so per shard)
+void retire_fused_plan(nl_engine *e, hipStream_t st) {
+    if (e->h_status) *e->h_status = 0;
+    if (e->tick) (void)hipMemsetAsync(e->tick + 1, 0, sizeof(unsigned), st);
+    e->fused = false;
+    e->fused_retired = true;
+}
+
 bool take_fused_timeout(nl_engine *e) {
     if (!e->h_status || !*e->h_status) return false;
     const unsigned st = *e->h_status;
-    *e->h_status = 0;
-    (void)hipMemsetAsync(e->tick + 1, 0, sizeof(unsigned), e->stream);
+    retire_fused_plan(e, e->stream);
     (void)hipStreamSynchronize(e->stream);
-    e->fused = false;
-    e->fused_retired = true;
     destroy_samp_graphs(e);
     e->fail(NL_OK, "warning: a fused-launch cluster exchange timed out (status %u); the step was redone on the general plan, "
                    "which this handle keeps from now on", st);
     if (!e->knobs.quiet) fprintf(stderr, "[nanollama_hip] %s\n", e->err.c_str());
     return true;
+}
+
+struct NoHook { int operator()() const { return NL_OK; } int operator()(int) const { return NL_OK; } };
+
+// THE redo of every entry point that steps the launch plans: body() queues the call's work and synchronises; when a fused launch
+// timed out in it (take_fused_timeout), on_redo() restores what the body does not rewrite and body() runs once more, on the general plan.
+template <class Body, class OnRedo = NoHook>
+int with_fused_redo(nl_engine *e, Body &&body, OnRedo &&on_redo = OnRedo{}) {
+    if (int rc = body()) return rc;
+    if (!take_fused_timeout(e)) return NL_OK;
+    if (int rc = on_redo()) return rc;
+    return body();
 }
 
 // ---- persistent greedy decode of the smallest tier (nl_persist.h) -----------------------------------------------------------
@@ -2470,18 +2487,16 @@ int decode_step(nl_engine *e, nl_engine::Batch &b, std::vector<nl_engine::StepGr
 }
 
 struct StepRow { int token, pos, stream; };
-struct NoHook { int operator()() const { return NL_OK; } int operator()(int) const { return NL_OK; } };
-
 // The single-token row loop of the batched entry points: n steps of the launch plan on e->stream, step j on row(j) (a StepRow, in
 // execution order) with whatever after_row(j) queues behind its launch; `before` runs at the head of every attempt, `tail` behind
-// the last step (the sampled paths: the block up and down), then the synchronise -- and once more from `before` on the general plan when a fused launch timed out
-// (take_fused_timeout: every buffer a step writes is rewritten).  Step j's control block is slot j % ctl_ring_cap of the pinned
+// the last step (the sampled paths: the block up and down), then the synchronise -- and once more from `before` when a fused launch timed out
+// (with_fused_redo: every buffer a step writes is rewritten).  Step j's control block is slot j % ctl_ring_cap of the pinned
 // ring, and the stream is drained before slot 0 is taken again; only a mixed step gets there: every other caller has
 // n <= max(seq_len, max_streams) = ctl_ring_cap.
 template <class Row, class AfterRow, class Before = NoHook, class Tail = NoHook>
 int single_steps(nl_engine *e, int n, Row &&row, AfterRow &&after_row, Before &&before = Before{}, Tail &&tail = Tail{}) {
-    int rc;
-    for (int attempt = 0;; attempt++) {
+    return with_fused_redo(e, [&]() -> int {
+        int rc;
         if ((rc = before())) return rc;
         for (int j = 0; j < n; j++) {
             const int slot = j % e->ctl_ring_cap;
@@ -2495,10 +2510,8 @@ int single_steps(nl_engine *e, int n, Row &&row, AfterRow &&after_row, Before &&
         }
         if ((rc = tail())) return rc;
         HIPCK(e, hipStreamSynchronize(e->stream));
-        if (attempt == 0 && take_fused_timeout(e)) continue;
-        break;
-    }
-    return NL_OK;
+        return NL_OK;
+    });
 }
 
 // The multi-token path of a prompt (nl_prefill, nl_score): tiles of e->bt.cap tokens on the matrix cores, causality from each
@@ -2604,6 +2617,109 @@ void group_stop(GroupCtl *g) {
 }
 
 int p2p_alloc_area(nl_engine *e);   // below (shared with nl_p2p_export)
+
+// One per-call step at (token, pos) of `stream`, for nl_forward (logits_out: the logits are in e->h_logits when it returns) and
+// nl_forward_argmax (next_id) alike, down THE tier ladder -- each rung a fall-back of the one above:
+//   1. the resident session takes the token (nl_persist.h: no launch, no weight fetch; the LM-head units store the logits into
+//      the pinned host buffer themselves)
+//   2. sessions off: one token as a persistent launch of one step (weights to the registers, one pass)
+//   3. the call box (call_step: no control copy, no synchronise; the logits rows are in the pinned buffer)
+//   4. control copy + launch_step + read-back + synchronise
+// with rungs 3 and 4 under the fused-plan redo, then the push all-reduce's status.
+int one_token(nl_engine *e, int stream, int token, int pos, float *logits_out, int *next_id) {
+    const bool want_logits = logits_out != nullptr;
+    // one GPU: the LM head stores the logits into the pinned buffer itself (ctl[CTL_HOSTOUT]); groups: a DMA behind the step.
+    // (The persistent rung asks for no more than the first two terms: where pd_usable holds the others are true.)
+    const bool direct = want_logits && e->d_h_logits && e->G == 1 && !e->knobs.force_tp_plan && !e->p2p.on;
+    const bool box_ok = direct || !want_logits;      // the call box leaves logits nowhere but in the pinned buffer
+    int *h_id = reinterpret_cast<int *>(e->h_logits + e->cfg.vocab);
+    auto fetch = [&](const int *d_id) -> int {       // what the caller asked for, queued behind the step
+        if (want_logits && !direct) HIPCK(e, hipMemcpyAsync(e->h_logits, e->logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToHost, e->stream));
+        if (next_id) HIPCK(e, hipMemcpyAsync(h_id, d_id, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPCK(e, hipStreamSynchronize(e->stream));
+        return NL_OK;
+    };
+    int rc;
+    bool served = false;
+    if ((rc = pd_session_step(e, stream, token, pos, want_logits, next_id, &served)) || served) return rc;
+    if (pd_usable(e, pos, 1)) {
+        if ((rc = note_positions(e, stream, pos, 1))) return rc;
+        if ((rc = pd_launch(e, stream, token, pos, 1, direct ? e->d_h_logits : nullptr))) return rc;
+        if ((rc = fetch(e->ids))) return rc;
+        if (!pd_take_timeout(e)) {
+            if (next_id) *next_id = *h_id;
+            return NL_OK;
+        }
+    }
+    rc = with_fused_redo(e, [&]() -> int {
+        int brc;
+        if ((brc = note_positions(e, stream, pos, 1))) return brc;
+        if (box_ok && call_step(e, token, pos, stream, direct ? 1 : 0, next_id ? h_id : nullptr, &brc)) return brc;
+        if ((brc = set_ctl(e, token, pos, 0, stream, direct ? 1 : 0))) return brc;
+        if ((brc = launch_step(e, pos))) return brc;
+        return fetch(e->result);
+    });
+    if (rc) return rc;
+    if (next_id) *next_id = *h_id;
+    return p2p_check(e);
+}
+
+// The length of a chain of n_steps steps from pos: what the context and the id buffer hold.
+int chain_len(const nl_engine *e, int pos, int n_steps) { return std::min(std::min(n_steps, e->cfg.seq_len - pos), e->ids_cap); }
+
+// m chained steps on e->stream: whole graphs of e->graph_steps steps while exec_for(i) yields one for the steps from i on
+// (nullptr: single steps from here), then step(i) for the rest, then the m ids behind the chain into ids_out.
+template <class ExecFor, class Step>
+int chain_steps(nl_engine *e, int m, int *ids_out, ExecFor &&exec_for, Step &&step) {
+    int i = 0;
+    while (i + e->graph_steps <= m) {
+        const hipGraphExec_t exec = exec_for(i);
+        if (!exec) break;
+        HIPCK(e, hipGraphLaunch(exec, e->stream));
+        i += e->graph_steps;
+    }
+    for (; i < m; i++)
+        if (int rc = step(i)) return rc;
+    HIPCK(e, hipMemcpyAsync(ids_out, e->ids, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    return NL_OK;
+}
+
+// An output (or in-out) buffer of a call on a group handle: every rank writes a copy of its own -- the ranks compute the same
+// values -- and rank 0's goes back to the caller when the call returned NL_OK.  n_in: elements every copy starts with.
+template <class T>
+struct PerRank {
+    T *user;
+    std::vector<std::vector<T>> copy;
+    PerRank(const nl_engine *lead, T *user, size_t cap, size_t n_in = 0) : user(user), copy(lead->grp->members.size(), std::vector<T>(std::max<size_t>(cap, 1))) {
+        if (n_in) for (auto &c : copy) memcpy(c.data(), user, std::min(n_in, c.size()) * sizeof(T));
+    }
+    T *operator[](int r) { return copy[r].data(); }
+    void back(int rc, size_t n) { if (rc == NL_OK && user) memcpy(user, copy[0].data(), n * sizeof(T)); }
+};
+
+// The device memory of one op-level call (the nl_op_* entry points: host in / out, a test's view of one kernel): typed allocations
+// and a sampler scratch, all freed when the call returns, whichever way it returns.
+struct OpScratch {
+    void *owned[8] = {};
+    int n_owned = 0;
+    nl::SampScratch samp;
+    void own(void *p) { owned[n_owned++] = p; }
+    template <class T> T *alloc(size_t count) {           // nullptr: the allocation failed
+        void *p = nullptr;
+        if (n_owned == 8 || hipMalloc(&p, count * sizeof(T)) != hipSuccess) return nullptr;
+        own(p);
+        return static_cast<T *>(p);
+    }
+    void free_all() {
+        samp_free(samp);
+        for (int i = 0; i < n_owned; i++) (void)hipFree(owned[i]);
+        n_owned = 0;
+    }
+    ~OpScratch() { free_all(); }
+};
+// (every failing HIP call of an op-level entry point is NL_ERR_HIP)
+#define OP_HIP(expr) do { if ((expr) != hipSuccess) return NL_ERR_HIP; } while (0)
+#define OP_ALLOC(ptr, S, T, count) do { if (!((ptr) = (S).alloc<T>(count))) return NL_ERR_HIP; } while (0)
 
 }  // namespace
 
@@ -3624,45 +3740,7 @@ int nl_forward(nl_handle e, int stream, int token, int pos, float *logits_out) {
     int rc = check_step_args(e, stream, token, pos);
     if (rc) return rc;
     HIPCK(e, hipSetDevice(e->dev));
-    {
-        // the smallest tier: the resident session takes the token (nl_persist.h: no launch, no weight fetch, the LM-head units
-        // store the logits into the pinned host buffer themselves)
-        bool served = false;
-        if ((rc = pd_session_step(e, stream, token, pos, logits_out != nullptr, nullptr, &served))) return rc;
-        if (served) {
-            if (logits_out && logits_out != e->h_logits) memcpy(logits_out, e->h_logits, (size_t)e->cfg.vocab * 4);
-            return NL_OK;
-        }
-    }
-    if (pd_usable(e, pos, 1)) {
-        // ... or, sessions off: one token as a persistent launch of one step (weights to the registers, one pass)
-        if ((rc = note_positions(e, stream, pos, 1))) return rc;
-        const bool direct = logits_out && e->d_h_logits;
-        if ((rc = pd_launch(e, stream, token, pos, 1, direct ? e->d_h_logits : nullptr))) return rc;
-        if (logits_out && !direct) HIPCK(e, hipMemcpyAsync(e->h_logits, e->logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCK(e, hipStreamSynchronize(e->stream));
-        if (!pd_take_timeout(e)) {
-            if (logits_out && logits_out != e->h_logits) memcpy(logits_out, e->h_logits, (size_t)e->cfg.vocab * 4);
-            return NL_OK;
-        }
-    }
-    for (int attempt = 0;; attempt++) {
-        if ((rc = note_positions(e, stream, pos, 1))) return rc;
-        // one GPU: the LM head stores the logits into the pinned buffer itself (ctl[CTL_HOSTOUT]); groups: a DMA behind the step
-        const bool direct = logits_out && e->d_h_logits && e->G == 1 && !e->knobs.force_tp_plan && !e->p2p.on;
-        if ((direct || !logits_out) && call_step(e, token, pos, stream, direct ? 1 : 0, nullptr, &rc)) {
-            if (rc) return rc;       // (the call box: no control copy, no synchronise; the logits rows are in the pinned buffer)
-        } else {
-            if ((rc = set_ctl(e, token, pos, 0, stream, direct ? 1 : 0))) return rc;
-            if ((rc = launch_step(e, pos))) return rc;
-            if (logits_out && !direct)
-                HIPCK(e, hipMemcpyAsync(e->h_logits, e->logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToHost, e->stream));
-            HIPCK(e, hipStreamSynchronize(e->stream));
-        }
-        if (attempt == 0 && take_fused_timeout(e)) continue;   // redo on the general plan
-        break;
-    }
-    if (int prc = p2p_check(e)) return prc;
+    if ((rc = one_token(e, stream, token, pos, logits_out, nullptr))) return rc;
     if (logits_out && logits_out != e->h_logits) memcpy(logits_out, e->h_logits, (size_t)e->cfg.vocab * 4);
     return NL_OK;
 }
@@ -3670,54 +3748,25 @@ int nl_forward(nl_handle e, int stream, int token, int pos, float *logits_out) {
 int nl_forward_argmax(nl_handle e, int stream, int token, int pos, int *next_id) {
     if (e && e->grp) {
         if (!next_id) return NL_ERR_INVALID;
-        int ids[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_forward_argmax(m, stream, token, pos, &ids[r]); });
-        *next_id = ids[0];
+        PerRank<int> id(e, next_id, 1);
+        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_forward_argmax(m, stream, token, pos, id[r]); });
+        id.back(rc, 1);
         return rc;
     }
     if (!e || !next_id) return NL_ERR_INVALID;
     int rc = check_step_args(e, stream, token, pos);
     if (rc) return rc;
     HIPCK(e, hipSetDevice(e->dev));
-    {
-        bool served = false;
-        if ((rc = pd_session_step(e, stream, token, pos, false, next_id, &served))) return rc;
-        if (served) return NL_OK;
-    }
-    if (pd_usable(e, pos, 1)) {          // (see nl_forward)
-        if ((rc = note_positions(e, stream, pos, 1))) return rc;
-        if ((rc = pd_launch(e, stream, token, pos, 1))) return rc;
-        int *h_id = reinterpret_cast<int *>(e->h_logits + e->cfg.vocab);
-        HIPCK(e, hipMemcpyAsync(h_id, e->ids, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-        HIPCK(e, hipStreamSynchronize(e->stream));
-        if (!pd_take_timeout(e)) { *next_id = *h_id; return NL_OK; }
-    }
-    for (int attempt = 0;; attempt++) {
-        if ((rc = note_positions(e, stream, pos, 1))) return rc;
-        int *h_id = reinterpret_cast<int *>(e->h_logits + e->cfg.vocab);
-        if (call_step(e, token, pos, stream, 0, h_id, &rc)) {
-            if (rc) return rc;
-        } else {
-            if ((rc = set_ctl(e, token, pos, 0, stream))) return rc;
-            if ((rc = launch_step(e, pos))) return rc;
-            HIPCK(e, hipMemcpyAsync(h_id, e->result, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-            HIPCK(e, hipStreamSynchronize(e->stream));
-        }
-        if (attempt == 0 && take_fused_timeout(e)) continue;   // redo on the general plan
-        *next_id = *h_id;
-        break;
-    }
-    if (int prc = p2p_check(e)) return prc;
-    return NL_OK;
+    return one_token(e, stream, token, pos, nullptr, next_id);
 }
 
 int nl_decode_greedy(nl_handle e, int stream, int token, int pos, int n_steps, int *ids_out, int *n_done) {
     if (e && e->grp) {
         if (!ids_out || n_steps < 0) return NL_ERR_INVALID;
-        std::vector<std::vector<int>> ids(e->grp->members.size(), std::vector<int>((size_t)std::max(n_steps, 1)));
-        int done[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_decode_greedy(m, stream, token, pos, n_steps, ids[r].data(), &done[r]); });
-        if (rc == NL_OK) { memcpy(ids_out, ids[0].data(), (size_t)done[0] * sizeof(int)); if (n_done) *n_done = done[0]; }
+        PerRank<int> ids(e, ids_out, (size_t)n_steps), done(e, n_done, 1);
+        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_decode_greedy(m, stream, token, pos, n_steps, ids[r], done[r]); });
+        ids.back(rc, (size_t)*done[0]);
+        done.back(rc, 1);
         return rc;
     }
     if (!e || !ids_out || n_steps < 0) return NL_ERR_INVALID;
@@ -3725,8 +3774,7 @@ int nl_decode_greedy(nl_handle e, int stream, int token, int pos, int n_steps, i
     if (rc) return rc;
     HIPCK(e, hipSetDevice(e->dev));
     if (int qrc = pd_session_close(e)) return qrc;
-    int n = std::min(n_steps, e->cfg.seq_len - pos);
-    n = std::min(n, e->ids_cap);
+    const int n = chain_len(e, pos, n_steps);
     if ((rc = note_positions(e, stream, pos, n))) return rc;
     int done = 0;
     if (n > 0 && pd_usable(e, pos, 1)) {
@@ -3740,21 +3788,15 @@ int nl_decode_greedy(nl_handle e, int stream, int token, int pos, int n_steps, i
     }
     if (done < n) {
         const int tok = done ? ids_out[done - 1] : token, p0 = pos + done, m = n - done;
-        for (int attempt = 0;; attempt++) {
-            if ((rc = set_ctl(e, tok, p0, 1, stream))) return rc;
-            int i = 0;
-            for (; i + e->graph_steps <= m && e->graph_steps > 1; i += e->graph_steps) {
-                nl_engine::PlanSet &S = pick_plan(e, p0 + i + e->graph_steps - 1);   // highest position of these steps
-                if (!S.multi_exec) break;
-                HIPCK(e, hipGraphLaunch(S.multi_exec, e->stream));
-            }
-            for (; i < m; i++)
-                if ((rc = launch_step(e, p0 + i))) return rc;
-            HIPCK(e, hipMemcpyAsync(ids_out + done, e->ids, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        rc = with_fused_redo(e, [&]() -> int {           // (a redo: the whole chain again, on the general plan)
+            if (int brc = set_ctl(e, tok, p0, 1, stream)) return brc;
+            // the 16-step graph of the plan that serves the highest position of its steps
+            auto exec_for = [&](int i) { return e->graph_steps > 1 ? pick_plan(e, p0 + i + e->graph_steps - 1).multi_exec : nullptr; };
+            if (int brc = chain_steps(e, m, ids_out + done, exec_for, [&](int i) { return launch_step(e, p0 + i); })) return brc;
             HIPCK(e, hipStreamSynchronize(e->stream));
-            if (attempt == 0 && take_fused_timeout(e)) continue;   // the whole chain again, on the general plan
-            break;
-        }
+            return NL_OK;
+        });
+        if (rc) return rc;
     }
     if (int prc = p2p_check(e)) return prc;
     if (n_done) *n_done = n;
@@ -3857,17 +3899,13 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
     if (e && e->grp) {
         // every rank samples from the same gathered logits with the same uniforms: the same ids; rank 0's results are returned
         if (!ids_out || !uniforms || !recent || !n_recent || !p || n_steps < 0) return NL_ERR_INVALID;
-        const size_t nr = e->grp->members.size(), cap = (size_t)std::max(p->rep_window, 1);
-        std::vector<std::vector<int>> ids(nr, std::vector<int>((size_t)std::max(n_steps, 1))), rec(nr, std::vector<int>(cap));
-        int nrec[8], done[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (size_t r = 0; r < nr; r++) { nrec[r] = *n_recent; memcpy(rec[r].data(), recent, std::min((size_t)std::max(*n_recent, 0), cap) * sizeof(int)); }
-        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_sample_decode(m, stream, pos, n_steps, p, uniforms, rec[r].data(), &nrec[r], ids[r].data(), &done[r]); });
-        if (rc == NL_OK) {
-            memcpy(ids_out, ids[0].data(), (size_t)done[0] * sizeof(int));
-            memcpy(recent, rec[0].data(), (size_t)std::max(nrec[0], 0) * sizeof(int));
-            *n_recent = nrec[0];
-            if (n_done) *n_done = done[0];
-        }
+        PerRank<int> ids(e, ids_out, (size_t)n_steps), done(e, n_done, 1), nrec(e, n_recent, 1, 1);
+        PerRank<int> rec(e, recent, (size_t)std::max(p->rep_window, 1), (size_t)std::max(*n_recent, 0));
+        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_sample_decode(m, stream, pos, n_steps, p, uniforms, rec[r], nrec[r], ids[r], done[r]); });
+        ids.back(rc, (size_t)*done[0]);
+        rec.back(rc, (size_t)std::max(*nrec[0], 0));
+        nrec.back(rc, 1);
+        done.back(rc, 1);
         return rc;
     }
     if (!e || !ids_out || !uniforms || !recent || !n_recent || n_steps < 0) return NL_ERR_INVALID;
@@ -3879,8 +3917,7 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
     if (*n_recent < 0 || *n_recent > p->rep_window) return e->fail(NL_ERR_INVALID, "n_recent %d exceeds rep_window %d", *n_recent, p->rep_window);
     HIPCK(e, hipSetDevice(e->dev));
     if (int qrc = pd_session_close(e)) return qrc;
-    int n = std::min(n_steps, e->cfg.seq_len - pos);
-    n = std::min(n, e->ids_cap);
+    const int n = chain_len(e, pos, n_steps);
     if (n_done) *n_done = std::max(n, 0);
     if (n <= 0) return NL_OK;
     if (!e->sp_ready || e->sp_uniforms_cap < n) {
@@ -3900,7 +3937,52 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
         if (!e->samp_keep) { std::lock_guard<std::mutex> setup(g_setup_mu); HIPCK(e, dalloc(&e->samp_keep, (size_t)e->cfg.vocab, &e->bytes_state)); }
         HIPCK(e, hipMemcpyAsync(e->samp_keep, e->logits, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
     }
-    for (int attempt = 0;; attempt++) {
+    // the 16-step graph for the steps from i on, or nullptr: single steps from there
+    auto exec_for = [&](int i) -> hipGraphExec_t {
+        if (!e->ps[0].multi_exec || e->samp_graph_failed) return nullptr;
+        // {sampler kernels, plan} x graph_steps as one graph per launch plan (its kernel arguments include the sampling
+        // parameters: re-captured when they change); the plan is chosen by the highest position of the 16 steps
+        const int k = plan_index(e, pos + i + e->graph_steps - 1);
+        if (!e->samp_graph_exec[k] || memcmp(&e->samp_graph_params[k], p, sizeof(*p)) != 0) {
+            std::lock_guard<std::mutex> setup(g_setup_mu);
+            if (e->samp_graph_exec[k]) { hipGraphExecDestroy(e->samp_graph_exec[k]); e->samp_graph_exec[k] = nullptr; }
+            if (e->samp_graph[k]) { hipGraphDestroy(e->samp_graph[k]); e->samp_graph[k] = nullptr; }
+            hipError_t cs = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
+            int rc2 = NL_OK;
+            // one GPU: the launch that picks the token also fetches its embedding row, and the plan's own embed and
+            // argmax launches (the argmax of logits nobody reads) are left out of the graph -- two launches per token
+            const bool tail = e->G == 1 && !e->p2p.on && !e->knobs.force_tp_plan && e->knobs.sample_embed;
+            for (int q = 0; cs == hipSuccess && q < e->graph_steps && !rc2; q++) {
+                if (launch_sample(s, e->logits, e->cfg.vocab, *p, e->ctl, e->ids, e->stream, tail ? &e->plan_embed : nullptr) != hipSuccess) rc2 = NL_ERR_HIP;
+                else if (!tail) rc2 = run_plan_eager(e, e->ps[k]);
+                else {
+                    for (const Op &op : e->ps[k].ops) {
+                        if (op.kind == K_EMBED || op.kind == K_ARGMAX) continue;
+                        const hipError_t ls = op.fn(e->stream);
+                        if (ls != hipSuccess) { rc2 = e->fail(NL_ERR_HIP, "launch %s: %s", kKindNames[op.kind], hipGetErrorString(ls)); break; }
+                    }
+                }
+            }
+            hipGraph_t g = nullptr;
+            if (cs == hipSuccess) cs = hipStreamEndCapture(e->stream, &g);
+            if (cs == hipSuccess && !rc2 && g && hipGraphInstantiate(&e->samp_graph_exec[k], g, nullptr, nullptr, 0) == hipSuccess) {
+                e->samp_graph[k] = g;
+                e->samp_graph_params[k] = *p;
+            } else {
+                if (g) hipGraphDestroy(g);
+                (void)hipGetLastError();
+                e->samp_graph_exec[k] = nullptr;
+                e->samp_graph_failed = true;      // (e.g. a library call that cannot be captured): eager launches below
+            }
+        }
+        return e->samp_graph_exec[k];
+    };
+    auto step = [&](int i) -> int {
+        HIPCK(e, launch_sample(s, e->logits, e->cfg.vocab, *p, e->ctl, e->ids, e->stream));
+        return launch_step(e, pos + i);
+    };
+    rc = with_fused_redo(e, [&]() -> int {
+        int rc;
         if ((rc = note_positions(e, stream, pos, n))) return rc;
         // ctl: the select kernel writes token = sampled id and pos + 1; the forward that follows runs unchained
         // (its argmax does not advance the state).  ctl.pos is primed to pos - 1 so the first increment lands on pos.
@@ -3910,60 +3992,15 @@ int nl_sample_decode(nl_handle e, int stream, int pos, int n_steps, const nl_sam
         if (n_recent_in > 0) HIPCK(e, hipMemcpyAsync(s.recent, recent, (size_t)n_recent_in * 4, hipMemcpyHostToDevice, e->stream));
         *n_recent = n_recent_in;
         HIPCK(e, hipMemcpyAsync(s.recent_n, n_recent, 4, hipMemcpyHostToDevice, e->stream));
-        int i = 0;
-        while (e->ps[0].multi_exec && !e->samp_graph_failed && i + e->graph_steps <= n) {
-            // {sampler kernels, plan} x graph_steps as one graph per launch plan (its kernel arguments include the sampling
-            // parameters: re-captured when they change); the plan is chosen by the highest position of the 16 steps
-            const int k = plan_index(e, pos + i + e->graph_steps - 1);
-            if (!e->samp_graph_exec[k] || memcmp(&e->samp_graph_params[k], p, sizeof(*p)) != 0) {
-                std::lock_guard<std::mutex> setup(g_setup_mu);
-                if (e->samp_graph_exec[k]) { hipGraphExecDestroy(e->samp_graph_exec[k]); e->samp_graph_exec[k] = nullptr; }
-                if (e->samp_graph[k]) { hipGraphDestroy(e->samp_graph[k]); e->samp_graph[k] = nullptr; }
-                hipError_t cs = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
-                int rc2 = NL_OK;
-                // one GPU: the launch that picks the token also fetches its embedding row, and the plan's own embed and
-                // argmax launches (the argmax of logits nobody reads) are left out of the graph -- two launches per token
-                const bool tail = e->G == 1 && !e->p2p.on && !e->knobs.force_tp_plan && e->knobs.sample_embed;
-                for (int q = 0; cs == hipSuccess && q < e->graph_steps && !rc2; q++) {
-                    if (launch_sample(s, e->logits, e->cfg.vocab, *p, e->ctl, e->ids, e->stream, tail ? &e->plan_embed : nullptr) != hipSuccess) rc2 = NL_ERR_HIP;
-                    else if (!tail) rc2 = run_plan_eager(e, e->ps[k]);
-                    else {
-                        for (const Op &op : e->ps[k].ops) {
-                            if (op.kind == K_EMBED || op.kind == K_ARGMAX) continue;
-                            const hipError_t ls = op.fn(e->stream);
-                            if (ls != hipSuccess) { rc2 = e->fail(NL_ERR_HIP, "launch %s: %s", kKindNames[op.kind], hipGetErrorString(ls)); break; }
-                        }
-                    }
-                }
-                hipGraph_t g = nullptr;
-                if (cs == hipSuccess) cs = hipStreamEndCapture(e->stream, &g);
-                if (cs == hipSuccess && !rc2 && g && hipGraphInstantiate(&e->samp_graph_exec[k], g, nullptr, nullptr, 0) == hipSuccess) {
-                    e->samp_graph[k] = g;
-                    e->samp_graph_params[k] = *p;
-                } else {
-                    if (g) hipGraphDestroy(g);
-                    (void)hipGetLastError();
-                    e->samp_graph_exec[k] = nullptr;
-                    e->samp_graph_failed = true;      // (e.g. a library call that cannot be captured): eager launches below
-                    break;
-                }
-            }
-            HIPCK(e, hipGraphLaunch(e->samp_graph_exec[k], e->stream));
-            i += e->graph_steps;
-        }
-        for (; i < n; i++) {
-            HIPCK(e, launch_sample(s, e->logits, e->cfg.vocab, *p, e->ctl, e->ids, e->stream));
-            if ((rc = launch_step(e, pos + i))) return rc;
-        }
-        HIPCK(e, hipMemcpyAsync(ids_out, e->ids, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        if ((rc = chain_steps(e, n, ids_out, exec_for, step))) return rc;
         HIPCK(e, hipMemcpyAsync(n_recent, s.recent_n, 4, hipMemcpyDeviceToHost, e->stream));
         HIPCK(e, hipStreamSynchronize(e->stream));
-        if (attempt == 0 && take_fused_timeout(e)) {
-            HIPCK(e, hipMemcpyAsync(e->logits, e->samp_keep, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
-            continue;
-        }
-        break;
-    }
+        return NL_OK;
+    }, [&]() -> int {        // a redo restarts from the logits this call found
+        HIPCK(e, hipMemcpyAsync(e->logits, e->samp_keep, (size_t)e->cfg.vocab * 4, hipMemcpyDeviceToDevice, e->stream));
+        return NL_OK;
+    });
+    if (rc) return rc;
     if (int prc = p2p_check(e)) return prc;
     if (*n_recent > 0) HIPCK(e, hipMemcpy(recent, s.recent, (size_t)*n_recent * 4, hipMemcpyDeviceToHost));
     return NL_OK;
@@ -3975,35 +4012,29 @@ int nl_op_sample(int device, float *logits, int vocab, const nl_sample_params *p
     int rc = check_sample_params(nullptr, p);
     if (rc) return rc;
     if (*n_recent < 0 || *n_recent > p->rep_window) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    SampScratch s;
-    float *d_logits = nullptr;
-    int *d_ctl = nullptr, *d_ids = nullptr;
-    rc = NL_ERR_HIP;
-    do {
-        if (samp_alloc(s, vocab, 1) != hipSuccess) break;
-        if (hipMalloc((void **)&d_logits, (size_t)vocab * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_ctl, CTL_WORDS * 4) != hipSuccess || hipMalloc((void **)&d_ids, 16) != hipSuccess) break;
-        if (hipMemset(d_ctl, 0, CTL_WORDS * 4) != hipSuccess) break;
-        if (hipMemcpy(d_logits, logits, (size_t)vocab * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(s.uniforms, &uniform, 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        const SampRow row = samp_row_of(*p);
-        if (hipMemcpy(s.row, &row, sizeof row, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (*n_recent > 0 && hipMemcpy(s.recent, recent, (size_t)*n_recent * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(s.recent_n, n_recent, 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (launch_sample(s, d_logits, vocab, *p, d_ctl, d_ids, (hipStream_t)0) != hipSuccess) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(picked, d_ids, 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (hipMemcpy(logits, d_logits, (size_t)vocab * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (hipMemcpy(n_recent, s.recent_n, 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (*n_recent > 0 && hipMemcpy(recent, s.recent, (size_t)*n_recent * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = NL_OK;
-    } while (0);
-    samp_free(s);
-    if (d_logits) (void)hipFree(d_logits);
-    if (d_ctl) (void)hipFree(d_ctl);
-    if (d_ids) (void)hipFree(d_ids);
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpScratch S;
+    SampScratch &s = S.samp;
+    float *d_logits;
+    int *d_ctl, *d_ids;
+    OP_HIP(samp_alloc(s, vocab, 1));
+    OP_ALLOC(d_logits, S, float, (size_t)vocab);
+    OP_ALLOC(d_ctl, S, int, CTL_WORDS);
+    OP_ALLOC(d_ids, S, int, 4);
+    OP_HIP(hipMemset(d_ctl, 0, CTL_WORDS * 4));
+    OP_HIP(hipMemcpy(d_logits, logits, (size_t)vocab * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(s.uniforms, &uniform, 4, hipMemcpyHostToDevice));
+    const SampRow row = samp_row_of(*p);
+    OP_HIP(hipMemcpy(s.row, &row, sizeof row, hipMemcpyHostToDevice));
+    if (*n_recent > 0) OP_HIP(hipMemcpy(s.recent, recent, (size_t)*n_recent * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(s.recent_n, n_recent, 4, hipMemcpyHostToDevice));
+    OP_HIP(launch_sample(s, d_logits, vocab, *p, d_ctl, d_ids, (hipStream_t)0));
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(picked, d_ids, 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(logits, d_logits, (size_t)vocab * 4, hipMemcpyDeviceToHost));
+    OP_HIP(hipMemcpy(n_recent, s.recent_n, 4, hipMemcpyDeviceToHost));
+    if (*n_recent > 0) OP_HIP(hipMemcpy(recent, s.recent, (size_t)*n_recent * 4, hipMemcpyDeviceToHost));
+    return NL_OK;
 }
 
 int nl_prefill(nl_handle e, int stream, const int *tokens, int n, int pos0, float *last_logits_out) {
@@ -4119,33 +4150,31 @@ int nl_op_score_rows(int device, const float *logits, int vocab, int n, const in
     for (int i = 0; i < n; i++)
         if (targets[i] < -1 || targets[i] >= vocab) return NL_ERR_INVALID;
     if (n == 0) return NL_OK;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    float *d_logits = nullptr, *d_lp = nullptr, *d_lse = nullptr;
-    int *d_t = nullptr, *d_am = nullptr;
-    int rc = NL_ERR_HIP;
-    do {
-        if (hipMalloc((void **)&d_logits, (size_t)n * vocab * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_lp, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_lse, (size_t)n * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_t, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_am, (size_t)n * 4) != hipSuccess) break;
-        if (hipMemcpy(d_logits, logits, (size_t)n * vocab * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_t, targets, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        // (poison: a row the kernel does not write does not go unseen)
-        if (hipMemset(d_lp, 0xff, (size_t)n * 4) != hipSuccess || hipMemset(d_lse, 0xff, (size_t)n * 4) != hipSuccess ||
-            hipMemset(d_am, 0xff, (size_t)n * 4) != hipSuccess) break;
-        const int slab = StepKnobs().score_slab;     // nl_score's launches: a slab of rows each, at the row pitch of its scratch
-        bool ok = true;
-        for (int first = 0; first < n && ok; first += slab) {
-            const ScoreRowsParams SP{d_logits + (size_t)first * vocab, vocab, vocab, d_t + first, d_lp + first, d_lse + first, d_am + first};
-            ok = launch_score_rows(SP, std::min(slab, n - first), (hipStream_t)0) == hipSuccess;
-        }
-        if (!ok || hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(logprob_out, d_lp, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (lse_out && hipMemcpy(lse_out, d_lse, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (argmax_out && hipMemcpy(argmax_out, d_am, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = NL_OK;
-    } while (0);
-    for (void *p : {(void *)d_logits, (void *)d_lp, (void *)d_lse, (void *)d_t, (void *)d_am}) if (p) (void)hipFree(p);
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpScratch S;
+    float *d_logits, *d_lp, *d_lse;
+    int *d_t, *d_am;
+    OP_ALLOC(d_logits, S, float, (size_t)n * vocab);
+    OP_ALLOC(d_lp, S, float, (size_t)n);
+    OP_ALLOC(d_lse, S, float, (size_t)n);
+    OP_ALLOC(d_t, S, int, (size_t)n);
+    OP_ALLOC(d_am, S, int, (size_t)n);
+    OP_HIP(hipMemcpy(d_logits, logits, (size_t)n * vocab * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d_t, targets, (size_t)n * 4, hipMemcpyHostToDevice));
+    // (poison: a row the kernel does not write does not go unseen)
+    OP_HIP(hipMemset(d_lp, 0xff, (size_t)n * 4));
+    OP_HIP(hipMemset(d_lse, 0xff, (size_t)n * 4));
+    OP_HIP(hipMemset(d_am, 0xff, (size_t)n * 4));
+    const int slab = StepKnobs().score_slab;     // nl_score's launches: a slab of rows each, at the row pitch of its scratch
+    for (int first = 0; first < n; first += slab) {
+        const ScoreRowsParams SP{d_logits + (size_t)first * vocab, vocab, vocab, d_t + first, d_lp + first, d_lse + first, d_am + first};
+        OP_HIP(launch_score_rows(SP, std::min(slab, n - first), (hipStream_t)0));
+    }
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(logprob_out, d_lp, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (lse_out) OP_HIP(hipMemcpy(lse_out, d_lse, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (argmax_out) OP_HIP(hipMemcpy(argmax_out, d_am, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return NL_OK;
 }
 
 namespace {
@@ -4161,9 +4190,9 @@ int nl_forward_batch(nl_handle e, const int *streams, const int *tokens, const i
                      int *next_ids) {
     if (e && e->grp) {
         if (n < 0) return NL_ERR_INVALID;
-        std::vector<std::vector<int>> ids(e->grp->members.size(), std::vector<int>((size_t)std::max(n, 1)));
-        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_forward_batch(m, streams, tokens, pos, n, r == 0 ? logits_out : nullptr, ids[r].data()); });
-        if (rc == NL_OK && next_ids) memcpy(next_ids, ids[0].data(), (size_t)n * sizeof(int));
+        PerRank<int> ids(e, next_ids, (size_t)n);
+        const int rc = group_run(e, [&](nl_engine *m, int r) { return nl_forward_batch(m, streams, tokens, pos, n, r == 0 ? logits_out : nullptr, ids[r]); });
+        ids.back(rc, (size_t)n);
         return rc;
     }
     if (!e || !streams || !tokens || !pos || n < 0) return NL_ERR_INVALID;
@@ -4573,35 +4602,31 @@ int nl_op_sample_rows(int device, float *logits, int vocab, int n, const nl_samp
     const SampBlock blk{L, h.data()};
     blk.pack(rows, n);
     const size_t lg_bytes = (size_t)n * vocab * 4;
-    SampScratch s;
-    float *d_logits = nullptr;
-    int *d_blk = nullptr;
-    int rc = NL_ERR_HIP;
-    do {
-        if (samp_alloc(s, vocab, 1, BS_MAX_ROWS) != hipSuccess) break;
-        if (hipMalloc((void **)&d_logits, lg_bytes) != hipSuccess || hipMalloc((void **)&d_blk, L.total * 4) != hipSuccess) break;
-        // poison every word a row's launches write before they read it (pmax, h1g, keys_in below the vocabulary): a kernel that
-        // read a word it did not write in this call would see 0xFF bytes here, where the handle's long-lived scratch holds the
-        // previous step's values.  The keys_in tail past the vocabulary keeps samp_alloc's zeroes: the select kernels load it
-        // and mask it.
-        const int nblocks = (vocab + 255) / 256;
-        const size_t kstride = (size_t)SAMP_THREADS * samp_chunk(vocab);
-        if (hipMemset(s.pmax, 0xFF, (size_t)nblocks * BS_MAX_ROWS * 4) != hipSuccess) break;
-        if (hipMemset(s.h1g, 0xFF, (size_t)2048 * 8 * BS_MAX_ROWS) != hipSuccess) break;
-        if (hipMemset2D(s.keys_in, kstride * 4, 0xFF, (size_t)vocab * 4, BS_MAX_ROWS) != hipSuccess) break;
-        if (hipMemcpy(d_logits, logits, lg_bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (blk.upload(d_blk, (hipStream_t)0) != hipSuccess) break;
-        if (launch_block_sample(s, vocab, d_blk, n, 0, n, d_logits, 7u, (hipStream_t)0) != hipSuccess) break;
-        if (hipDeviceSynchronize() != hipSuccess) break;
-        if (blk.download(d_blk, (hipStream_t)0) != hipSuccess || hipStreamSynchronize((hipStream_t)0) != hipSuccess) break;
-        if (hipMemcpy(logits, d_logits, lg_bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
-        blk.unpack(rows, n, picked);
-        rc = NL_OK;
-    } while (0);
-    samp_free(s);
-    if (d_logits) (void)hipFree(d_logits);
-    if (d_blk) (void)hipFree(d_blk);
-    return rc;
+    OpScratch S;
+    SampScratch &s = S.samp;
+    float *d_logits;
+    int *d_blk;
+    OP_HIP(samp_alloc(s, vocab, 1, BS_MAX_ROWS));
+    OP_ALLOC(d_logits, S, float, (size_t)n * vocab);
+    OP_ALLOC(d_blk, S, int, L.total);
+    // poison every word a row's launches write before they read it (pmax, h1g, keys_in below the vocabulary): a kernel that
+    // read a word it did not write in this call would see 0xFF bytes here, where the handle's long-lived scratch holds the
+    // previous step's values.  The keys_in tail past the vocabulary keeps samp_alloc's zeroes: the select kernels load it
+    // and mask it.
+    const int nblocks = (vocab + 255) / 256;
+    const size_t kstride = (size_t)SAMP_THREADS * samp_chunk(vocab);
+    OP_HIP(hipMemset(s.pmax, 0xFF, (size_t)nblocks * BS_MAX_ROWS * 4));
+    OP_HIP(hipMemset(s.h1g, 0xFF, (size_t)2048 * 8 * BS_MAX_ROWS));
+    OP_HIP(hipMemset2D(s.keys_in, kstride * 4, 0xFF, (size_t)vocab * 4, BS_MAX_ROWS));
+    OP_HIP(hipMemcpy(d_logits, logits, lg_bytes, hipMemcpyHostToDevice));
+    OP_HIP(blk.upload(d_blk, (hipStream_t)0));
+    OP_HIP(launch_block_sample(s, vocab, d_blk, n, 0, n, d_logits, 7u, (hipStream_t)0));
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(blk.download(d_blk, (hipStream_t)0));
+    OP_HIP(hipStreamSynchronize((hipStream_t)0));
+    OP_HIP(hipMemcpy(logits, d_logits, lg_bytes, hipMemcpyDeviceToHost));
+    blk.unpack(rows, n, picked);
+    return NL_OK;
 }
 
 int nl_synchronize(nl_handle e) {
@@ -4648,14 +4673,14 @@ int nl_profile_forward(nl_handle e, int stream, int token, int pos, int iters, f
     for (int k = 0; k < NL_NUM_KINDS; k++) { ms_out[k] = 0.f; calls_out[k] = 0; }
     if ((rc = note_positions(e, stream, pos, 1))) return rc;
     if ((rc = set_ctl(e, token, pos, 0, stream))) return rc;
-    const nl_engine::PlanSet *Sp = &pick_plan(e, pos);   // the plan a step at this position runs
-    if ((rc = run_plan_eager(e, *Sp))) return rc;
-    HIPCK(e, hipStreamSynchronize(e->stream));
-    if (take_fused_timeout(e)) {
-        Sp = &pick_plan(e, pos);
-        if ((rc = run_plan_eager(e, *Sp))) return rc;
+    const nl_engine::PlanSet *Sp = nullptr;
+    rc = with_fused_redo(e, [&]() -> int {
+        Sp = &pick_plan(e, pos);                         // the plan a step at this position runs
+        if (int prc = run_plan_eager(e, *Sp)) return prc;
         HIPCK(e, hipStreamSynchronize(e->stream));
-    }
+        return NL_OK;
+    });
+    if (rc) return rc;
     const nl_engine::PlanSet &S = *Sp;
     for (const Op &op : S.ops) {
         HIPCK(e, hipEventRecord(e->ev0, e->stream));
@@ -4743,6 +4768,8 @@ int nl_debug_stamps(nl_handle e, int kind, long long *out /* 16 waves x 8 */) {
     if (int qrc = pd_session_close(e)) return qrc;
     long long *d = nullptr;
     HIPCK(e, hipMalloc((void **)&d, 128 * sizeof(long long)));
+    OpScratch S;
+    S.own(d);
     HIPCK(e, hipMemset(d, 0, 128 * sizeof(long long)));
     const nl_config &c = e->cfg;
     nl_engine::Layer &L = e->layers[0];
@@ -4774,14 +4801,41 @@ int nl_debug_stamps(nl_handle e, int kind, long long *out /* 16 waves x 8 */) {
             }
     }
     (void)c;
-    if (s != hipSuccess) { hipFree(d); return e->fail(NL_ERR_HIP, "debug launch: %s", hipGetErrorString(s)); }
+    if (s != hipSuccess) return e->fail(NL_ERR_HIP, "debug launch: %s", hipGetErrorString(s));
     HIPCK(e, hipStreamSynchronize(e->stream));
     HIPCK(e, hipMemcpy(out, d, 128 * sizeof(long long), hipMemcpyDeviceToHost));
-    hipFree(d);
     return NL_OK;
 }
 
 // ---- op-level entry points ---------------------------------------------------
+
+namespace {
+// What nl_op_matmul and nl_op_matmul_batch share: a temporary engine on a stream of its own, the packed matrix, the raw tensor
+// behind it.  open() makes them; the caller queues the raw bytes and its own input on st, then pack().
+struct OpMatrix {
+    nl_engine tmp;
+    hipStream_t st = nullptr;
+    PackedMat m;
+    OpScratch S;
+    uint8_t *d_raw = nullptr;
+    int type, rows, cols;
+    OpMatrix(uint32_t type, int rows, int cols) : type((int)type), rows(rows), cols(cols) { tmp.hd = 64; }
+    int open(uint64_t nbytes) {
+        OP_HIP(hipStreamCreate(&st));
+        tmp.stream = st;
+        OP_HIP(alloc_packed(&tmp, m, type, (rows + TR - 1) / TR, rows, cols));
+        OP_ALLOC(d_raw, S, uint8_t, nbytes);
+        return NL_OK;
+    }
+    int pack() { OP_HIP(repack(&tmp, m, d_raw, type, cols, 0, rows, 0, cols, 0, m.ntiles, ROWMAP_IDENT)); return NL_OK; }
+    ~OpMatrix() {
+        for (void *c : tmp.arena_chunks) hipFree(c);
+        S.free_all();
+        if (st) hipStreamDestroy(st);
+        tmp.stream = nullptr;
+    }
+};
+}  // namespace
 
 int nl_op_matmul(int device, uint32_t type, const void *w, uint64_t nbytes, const float *x, float *out, int rows,
                  int cols) {
@@ -4789,43 +4843,25 @@ int nl_op_matmul(int device, uint32_t type, const void *w, uint64_t nbytes, cons
     if (!type_supported(type)) return NL_ERR_UNSUPPORTED;  // matmulDispatch default arm, go/model.go:383-385
     if (is_kquant(type) && cols % 256) return NL_ERR_INVALID;
     if (raw_bytes(type, (uint64_t)rows * cols) != nbytes) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    nl_engine tmp;
-    tmp.hd = 64;
-    hipStream_t st;
-    if (hipStreamCreate(&st) != hipSuccess) return NL_ERR_HIP;
-    tmp.stream = st;
-    PackedMat m;
-    uint8_t *d_raw = nullptr;
-    float *d_x = nullptr, *d_out = nullptr;
-    int rc = NL_ERR_HIP;
-    do {
-        if (alloc_packed(&tmp, m, (int)type, (rows + TR - 1) / TR, rows, cols) != hipSuccess) break;
-        if (hipMalloc((void **)&d_raw, nbytes) != hipSuccess) break;
-        if (hipMalloc((void **)&d_x, (size_t)cols * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_out, (size_t)rows * 4) != hipSuccess) break;
-        if (hipMemcpyAsync(d_raw, w, nbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_x, x, (size_t)cols * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (repack(&tmp, m, d_raw, (int)type, cols, 0, rows, 0, cols, 0, m.ntiles, ROWMAP_IDENT) != hipSuccess) break;
-        GemvParams P{};
-        P.q0 = m.q; P.s0 = m.s; P.rows = rows; P.cols = cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
-        choose_geometry(&tmp, m, P.tw, P.kw);
-        P.x = d_x; P.out = d_out;
-        if (launch_gemv_t<PRO_PLAIN, EPI_STORE>(m.wtype, P, st) != hipSuccess) break;
-        if (hipMemcpyAsync(out, d_out, (size_t)rows * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = NL_OK;
-    } while (0);
-    for (void *c : tmp.arena_chunks) hipFree(c);
-    if (d_raw) hipFree(d_raw);
-    if (d_x) hipFree(d_x);
-    if (d_out) hipFree(d_out);
-    hipStreamDestroy(st);
-    tmp.stream = nullptr;
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpMatrix M(type, rows, cols);
+    if (int rc = M.open(nbytes)) return rc;
+    const PackedMat &m = M.m;
+    float *d_x, *d_out;
+    OP_ALLOC(d_x, M.S, float, (size_t)cols);
+    OP_ALLOC(d_out, M.S, float, (size_t)rows);
+    OP_HIP(hipMemcpyAsync(M.d_raw, w, nbytes, hipMemcpyHostToDevice, M.st));
+    OP_HIP(hipMemcpyAsync(d_x, x, (size_t)cols * 4, hipMemcpyHostToDevice, M.st));
+    if (int rc = M.pack()) return rc;
+    GemvParams P{};
+    P.q0 = m.q; P.s0 = m.s; P.rows = rows; P.cols = cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
+    choose_geometry(&M.tmp, m, P.tw, P.kw);
+    P.x = d_x; P.out = d_out;
+    OP_HIP((launch_gemv_t<PRO_PLAIN, EPI_STORE>(m.wtype, P, M.st)));
+    OP_HIP(hipMemcpyAsync(out, d_out, (size_t)rows * 4, hipMemcpyDeviceToHost, M.st));
+    OP_HIP(hipStreamSynchronize(M.st));
+    return NL_OK;
 }
-
-
 
 // Multi-token matmul through the MFMA path: out[n][rows] = W @ x[n] for n_tokens vectors (host in/out).
 int nl_op_matmul_batch(int device, uint32_t type, const void *w, uint64_t nbytes, const float *x, float *out,
@@ -4833,43 +4869,26 @@ int nl_op_matmul_batch(int device, uint32_t type, const void *w, uint64_t nbytes
     if (!w || !x || !out || rows <= 0 || cols <= 0 || cols % 32 || n_tokens <= 0) return NL_ERR_INVALID;
     if (device_type((int)type) != WT_Q4_0 && device_type((int)type) != WT_Q8_0 && type != WT_F16) return NL_ERR_UNSUPPORTED;
     if (raw_bytes(type, (uint64_t)rows * cols) != nbytes) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    nl_engine tmp;
-    tmp.hd = 64;
-    hipStream_t st;
-    if (hipStreamCreate(&st) != hipSuccess) return NL_ERR_HIP;
-    tmp.stream = st;
-    PackedMat m;
-    uint8_t *d_raw = nullptr;
-    float *d_x = nullptr, *d_out = nullptr;
-    uint4 *d_xf = nullptr;
-    int rc = NL_ERR_HIP;
-    do {
-        if (alloc_packed(&tmp, m, (int)type, (rows + TR - 1) / TR, rows, cols) != hipSuccess) break;
-        if (hipMalloc((void **)&d_raw, nbytes) != hipSuccess) break;
-        if (hipMalloc((void **)&d_x, (size_t)cols * n_tokens * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_out, (size_t)rows * n_tokens * 4) != hipSuccess) break;
-        if (hipMemcpyAsync(d_raw, w, nbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_x, x, (size_t)cols * n_tokens * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (repack(&tmp, m, d_raw, (int)type, cols, 0, rows, 0, cols, 0, m.ntiles, ROWMAP_IDENT) != hipSuccess) break;
-        QGemmParams P{};
-        P.q = m.q; P.s = m.s; P.rows = rows; P.cols = cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
-        if (hipMalloc((void **)&d_xf, xfrag_uint4(cols, n_tokens) * sizeof(uint4)) != hipSuccess) break;
-        if (launch_xsplit(m.wtype, d_x, cols, cols, n_tokens, d_xf, st) != hipSuccess) break;
-        P.xf = d_xf; P.n_tokens = n_tokens; P.out = d_out; P.ldo = rows;
-        if (launch_qgemm(m.wtype, P, StepKnobs{}, st) != hipSuccess) break;
-        if (hipMemcpyAsync(out, d_out, (size_t)rows * n_tokens * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = NL_OK;
-    } while (0);
-    for (void *c : tmp.arena_chunks) hipFree(c);
-    if (d_raw) hipFree(d_raw);
-    if (d_xf) hipFree(d_xf);
-    if (d_x) hipFree(d_x);
-    if (d_out) hipFree(d_out);
-    hipStreamDestroy(st);
-    tmp.stream = nullptr;
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpMatrix M(type, rows, cols);
+    if (int rc = M.open(nbytes)) return rc;
+    const PackedMat &m = M.m;
+    float *d_x, *d_out;
+    uint4 *d_xf;
+    OP_ALLOC(d_x, M.S, float, (size_t)cols * n_tokens);
+    OP_ALLOC(d_out, M.S, float, (size_t)rows * n_tokens);
+    OP_HIP(hipMemcpyAsync(M.d_raw, w, nbytes, hipMemcpyHostToDevice, M.st));
+    OP_HIP(hipMemcpyAsync(d_x, x, (size_t)cols * n_tokens * 4, hipMemcpyHostToDevice, M.st));
+    if (int rc = M.pack()) return rc;
+    QGemmParams P{};
+    P.q = m.q; P.s = m.s; P.rows = rows; P.cols = cols; P.npairs = m.npairs; P.ntiles = m.ntiles;
+    OP_ALLOC(d_xf, M.S, uint4, xfrag_uint4(cols, n_tokens));
+    OP_HIP(launch_xsplit(m.wtype, d_x, cols, cols, n_tokens, d_xf, M.st));
+    P.xf = d_xf; P.n_tokens = n_tokens; P.out = d_out; P.ldo = rows;
+    OP_HIP(launch_qgemm(m.wtype, P, StepKnobs{}, M.st));
+    OP_HIP(hipMemcpyAsync(out, d_out, (size_t)rows * n_tokens * 4, hipMemcpyDeviceToHost, M.st));
+    OP_HIP(hipStreamSynchronize(M.st));
+    return NL_OK;
 }
 
 namespace {
@@ -4889,20 +4908,16 @@ __global__ void rmsnorm_op_kernel(const float *x, const float *w, float eps, flo
 
 int nl_op_rmsnorm(int device, const float *x, const float *w, float eps, float *out, int n) {
     if (!x || !w || !out || n <= 0) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    float *d = nullptr;
-    if (hipMalloc((void **)&d, (size_t)n * 12) != hipSuccess) return NL_ERR_HIP;
-    int rc = NL_ERR_HIP;
-    do {
-        if (hipMemcpy(d, x, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d + n, w, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        hipLaunchKernelGGL(rmsnorm_op_kernel, dim3(1), dim3(256), 0, 0, d, d + n, eps, d + 2 * n, n);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpy(out, d + 2 * n, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = NL_OK;
-    } while (0);
-    hipFree(d);
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpScratch S;
+    float *d;
+    OP_ALLOC(d, S, float, (size_t)n * 3);
+    OP_HIP(hipMemcpy(d, x, (size_t)n * 4, hipMemcpyHostToDevice));
+    OP_HIP(hipMemcpy(d + n, w, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(rmsnorm_op_kernel, dim3(1), dim3(256), 0, 0, d, d + n, eps, d + 2 * n, n);
+    OP_HIP(hipGetLastError());
+    OP_HIP(hipMemcpy(out, d + 2 * n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return NL_OK;
 }
 
 namespace {
@@ -4914,66 +4929,56 @@ __global__ void exp_op_kernel(const float *x, float *out, int n) {
 // float32(exp(float64(x))) as the forward kernels compute it (exp_f64_as_f32, nl_kernels.h): parity tests only.
 int nl_op_exp(int device, const float *x, float *out, int n) {
     if (!x || !out || n <= 0) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    float *d = nullptr;
-    if (hipMalloc((void **)&d, (size_t)n * 8) != hipSuccess) return NL_ERR_HIP;
-    int rc = NL_ERR_HIP;
-    do {
-        if (hipMemcpy(d, x, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        hipLaunchKernelGGL(exp_op_kernel, dim3(1024), dim3(256), 0, 0, d, d + n, n);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpy(out, d + n, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = NL_OK;
-    } while (0);
-    hipFree(d);
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpScratch S;
+    float *d;
+    OP_ALLOC(d, S, float, (size_t)n * 2);
+    OP_HIP(hipMemcpy(d, x, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(exp_op_kernel, dim3(1024), dim3(256), 0, 0, d, d + n, n);
+    OP_HIP(hipGetLastError());
+    OP_HIP(hipMemcpy(out, d + n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return NL_OK;
 }
 
 // Soak of the 16-byte granule form (nl_tp.h gran16_soak_kernel): pairs writers on `n` compute units with readers on other XCDs.
 int nl_op_gran16_soak(int device, int n, unsigned iters, unsigned long long *torn, unsigned long long *seen) {
     if (!torn || !seen || n < 1 || n > 128 || iters < 1) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    u32x4 *slots = nullptr;
-    unsigned long long *cnt = nullptr;
-    int rc = NL_ERR_HIP;
-    do {
-        if (hipMalloc((void **)&slots, (size_t)n * 256 * sizeof(u32x4)) != hipSuccess || hipMalloc((void **)&cnt, 16) != hipSuccess) break;
-        if (hipMemset(slots, 0, (size_t)n * 256 * sizeof(u32x4)) != hipSuccess || hipMemset(cnt, 0, 16) != hipSuccess) break;
-        hipLaunchKernelGGL(gran16_soak_kernel, dim3(2 * n), dim3(256), 0, 0, slots, n, iters, cnt, cnt + 1);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
-        unsigned long long h[2];
-        if (hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) break;
-        *torn = h[0]; *seen = h[1];
-        rc = NL_OK;
-    } while (0);
-    if (slots) hipFree(slots);
-    if (cnt) hipFree(cnt);
-    return rc;
+    OP_HIP(hipSetDevice(device));
+    OpScratch S;
+    u32x4 *slots;
+    unsigned long long *cnt, h[2];
+    OP_ALLOC(slots, S, u32x4, (size_t)n * 256);
+    OP_ALLOC(cnt, S, unsigned long long, 2);
+    OP_HIP(hipMemset(slots, 0, (size_t)n * 256 * sizeof(u32x4)));
+    OP_HIP(hipMemset(cnt, 0, 16));
+    hipLaunchKernelGGL(gran16_soak_kernel, dim3(2 * n), dim3(256), 0, 0, slots, n, iters, cnt, cnt + 1);
+    OP_HIP(hipGetLastError());
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost));
+    *torn = h[0]; *seen = h[1];
+    return NL_OK;
 }
 
 // Soak of the in-XCD 16-byte granule form of the persistent decode's h hand-off (nl_persist.h pd_gran16_soak_local_kernel): 256
 // blocks, `pairs` writer / reader pairs per XCD as placement turns out (the rest leave at once).
 int nl_op_gran16_soak_local(int device, int pairs, unsigned iters, unsigned long long *torn, unsigned long long *seen) {
     if (!torn || !seen || pairs < 1 || pairs > PD_CUS / 2 || iters < 1 || iters > (1u << 24)) return NL_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return NL_ERR_HIP;
-    pd_u32x4 *slots = nullptr;
-    unsigned long long *cnt = nullptr;      // [0] torn, [1] seen, then the XCDs' ticket words
+    OP_HIP(hipSetDevice(device));
+    OpScratch S;
+    pd_u32x4 *slots;
+    unsigned long long *cnt, h[2];          // [0] torn, [1] seen, then the XCDs' ticket words
     const size_t nslot = (size_t)PD_XCDS * pairs * 256;
-    int rc = NL_ERR_HIP;
-    do {
-        if (hipMalloc((void **)&slots, nslot * sizeof(pd_u32x4)) != hipSuccess || hipMalloc((void **)&cnt, 64) != hipSuccess) break;
-        if (hipMemset(slots, 0, nslot * sizeof(pd_u32x4)) != hipSuccess || hipMemset(cnt, 0, 64) != hipSuccess) break;
-        hipLaunchKernelGGL(pd_gran16_soak_local_kernel, dim3(PD_GRID), dim3(256), 0, 0, slots, reinterpret_cast<unsigned *>(cnt + 2), pairs, iters,
-                           iters * 64u + 1000000u, cnt, cnt + 1);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
-        unsigned long long h[2];
-        if (hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) break;
-        *torn = h[0]; *seen = h[1];
-        rc = NL_OK;
-    } while (0);
-    if (slots) hipFree(slots);
-    if (cnt) hipFree(cnt);
-    return rc;
+    OP_ALLOC(slots, S, pd_u32x4, nslot);
+    OP_ALLOC(cnt, S, unsigned long long, 8);
+    OP_HIP(hipMemset(slots, 0, nslot * sizeof(pd_u32x4)));
+    OP_HIP(hipMemset(cnt, 0, 64));
+    hipLaunchKernelGGL(pd_gran16_soak_local_kernel, dim3(PD_GRID), dim3(256), 0, 0, slots, reinterpret_cast<unsigned *>(cnt + 2), pairs, iters,
+                       iters * 64u + 1000000u, cnt, cnt + 1);
+    OP_HIP(hipGetLastError());
+    OP_HIP(hipDeviceSynchronize());
+    OP_HIP(hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost));
+    *torn = h[0]; *seen = h[1];
+    return NL_OK;
 }
 
 // ---- in-process tensor-parallel group ----------------------------------------
@@ -5040,13 +5045,7 @@ int nl_group_forward(nl_handle *hs, int n, int stream, int token, int pos, float
         for (int r = 0; r < n; r++)
             if (hs[r]->h_status && *hs[r]->h_status) redo = true;
         if (attempt == 0 && redo) {          // a cluster exchange gave up in some shard: every shard retires the fused plan
-            for (int r = 0; r < n; r++) {
-                nl_engine *e = hs[r];
-                if (e->h_status) *e->h_status = 0;
-                if (e->tick) (void)hipMemsetAsync(e->tick + 1, 0, sizeof(unsigned), st);
-                e->fused = false;
-                e->fused_retired = true;
-            }
+            for (int r = 0; r < n; r++) retire_fused_plan(hs[r], st);
             HIPCK(e0, hipStreamSynchronize(st));
             e0->fail(NL_OK, "warning: a fused-launch cluster exchange timed out in the shard group; the step was redone on the general plan");
             continue;

@@ -37,6 +37,7 @@
 #include <optional>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace { void samp_free(nl::SampScratch &s); int voice_dir_alloc(nl_engine *e); }
@@ -265,10 +266,6 @@ struct Op {
     size_t count;
     std::function<hipError_t(hipStream_t)> fn;
     float *add_to = nullptr;
-    // GEMV launches keep their parameters here so a later pass can point each one at its successor
-    bool is_gemv = false;
-    int wtype = 0, pro = 0, epi = 0;
-    GemvParams gp{};
 };
 
 }  // namespace
@@ -666,53 +663,25 @@ GemvParams base_params(const nl_engine *e, const PackedMat &m, int mats = 1) {
     return P;
 }
 
-template <int HD>
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v; false: v is none of them (the exact value set of a kernel)
+template <int... Vs, typename F>
+bool dispatch_int(int v, F &&f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// ROPE without FIN: several position splits per token with the RoPE prologue (decode batches at positions >= 128, AttnParams::rp)
+template <int HD, bool FIN, bool ROPE>
 hipError_t launch_attn_hd(int gqa, AttnParams P, dim3 grid, hipStream_t st) {
-    switch (gqa) {
-    case 1: hipLaunchKernelGGL((attn_kernel<HD, 1>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 2: hipLaunchKernelGGL((attn_kernel<HD, 2>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 3: hipLaunchKernelGGL((attn_kernel<HD, 3>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 4: hipLaunchKernelGGL((attn_kernel<HD, 4>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 6: hipLaunchKernelGGL((attn_kernel<HD, 6>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 8: hipLaunchKernelGGL((attn_kernel<HD, 8>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-template <int HD>
-hipError_t launch_attn_fin_hd(int gqa, AttnParams P, dim3 grid, hipStream_t st) {
-    switch (gqa) {
-    case 1: hipLaunchKernelGGL((attn_kernel<HD, 1, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 2: hipLaunchKernelGGL((attn_kernel<HD, 2, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 3: hipLaunchKernelGGL((attn_kernel<HD, 3, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 4: hipLaunchKernelGGL((attn_kernel<HD, 4, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 6: hipLaunchKernelGGL((attn_kernel<HD, 6, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 8: hipLaunchKernelGGL((attn_kernel<HD, 8, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-// several position splits per token with the RoPE prologue (decode batches at positions >= 128, AttnParams::rp)
-template <int HD>
-hipError_t launch_attn_rope_hd(int gqa, AttnParams P, dim3 grid, hipStream_t st) {
-    switch (gqa) {
-    case 1: hipLaunchKernelGGL((attn_kernel<HD, 1, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 2: hipLaunchKernelGGL((attn_kernel<HD, 2, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 3: hipLaunchKernelGGL((attn_kernel<HD, 3, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 4: hipLaunchKernelGGL((attn_kernel<HD, 4, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 6: hipLaunchKernelGGL((attn_kernel<HD, 6, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    case 8: hipLaunchKernelGGL((attn_kernel<HD, 8, false, true>), grid, dim3(ATT_THREADS), 0, st, P); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = dispatch_int<1, 2, 3, 4, 6, 8>(gqa, [&](auto g) {
+        hipLaunchKernelGGL((attn_kernel<HD, decltype(g)::value, FIN, ROPE>), grid, dim3(ATT_THREADS), 0, st, P);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_attn(int hd, int gqa, AttnParams P, dim3 grid, hipStream_t st) {
-    if (P.rp.on) return hd == 64 ? launch_attn_rope_hd<64>(gqa, P, grid, st) : hd == 32 ? launch_attn_rope_hd<32>(gqa, P, grid, st) : hipErrorInvalidValue;
-    if (hd == 64) return launch_attn_hd<64>(gqa, P, grid, st);
-    if (hd == 32) return launch_attn_hd<32>(gqa, P, grid, st);
+    if (P.rp.on) return hd == 64 ? launch_attn_hd<64, false, true>(gqa, P, grid, st) : hd == 32 ? launch_attn_hd<32, false, true>(gqa, P, grid, st) : hipErrorInvalidValue;
+    if (hd == 64) return launch_attn_hd<64, false, false>(gqa, P, grid, st);
+    if (hd == 32) return launch_attn_hd<32, false, false>(gqa, P, grid, st);
     return hipErrorInvalidValue;
 }
 
@@ -730,31 +699,19 @@ void launch_attn_tile_g(const AttnParams &P, int n, int kvs, int nsplit, hipStre
 // mixed steps: the segment-tile kernel over the host's work list (grid: kv head x entry)
 template <int HD>
 hipError_t launch_attn_seg_hd(int gqa, const AttnParams &P, const int2 *work, int kvs, int n_work, hipStream_t st) {
-    const dim3 grid(kvs, n_work);
-    switch (gqa) {
-    case 1: hipLaunchKernelGGL((attn_seg_kernel<HD, 1, AttnTileQT<1>::value>), grid, dim3(AttnTileQT<1>::value * 1 * 4), 0, st, P, work); break;
-    case 2: hipLaunchKernelGGL((attn_seg_kernel<HD, 2, AttnTileQT<2>::value>), grid, dim3(AttnTileQT<2>::value * 2 * 4), 0, st, P, work); break;
-    case 3: hipLaunchKernelGGL((attn_seg_kernel<HD, 3, AttnTileQT<3>::value>), grid, dim3(AttnTileQT<3>::value * 3 * 4), 0, st, P, work); break;
-    case 4: hipLaunchKernelGGL((attn_seg_kernel<HD, 4, AttnTileQT<4>::value>), grid, dim3(AttnTileQT<4>::value * 4 * 4), 0, st, P, work); break;
-    case 8: hipLaunchKernelGGL((attn_seg_kernel<HD, 8, AttnTileQT<8>::value>), grid, dim3(AttnTileQT<8>::value * 8 * 4), 0, st, P, work); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = dispatch_int<1, 2, 3, 4, 8>(gqa, [&](auto g) {
+        constexpr int G = decltype(g)::value, QT = AttnTileQT<G>::value;
+        hipLaunchKernelGGL((attn_seg_kernel<HD, G, QT>), dim3(kvs, n_work), dim3(QT * G * 4), 0, st, P, work);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 inline int attn_tile_qt(int gqa) { return gqa == 1 ? 64 : gqa == 2 ? 32 : gqa == 8 ? 8 : 16; }   // = AttnTileQT<G>::value
 inline int attn_tile16_qt(int gqa) { return NL_ATT16_MUL * (gqa == 1 ? 64 : gqa == 2 ? 32 : gqa == 8 ? 8 : 16); }   // = AttnTile16QT<G>::value
 inline bool attn_tile_supported(int gqa) { return gqa == 1 || gqa == 2 || gqa == 3 || gqa == 4 || gqa == 8; }
 template <int HD>
 hipError_t launch_attn_tile_hd(int gqa, const AttnParams &P, int n, int kvs, int nsplit, hipStream_t st) {
-    switch (gqa) {
-    case 1: launch_attn_tile_g<HD, 1>(P, n, kvs, nsplit, st); break;
-    case 2: launch_attn_tile_g<HD, 2>(P, n, kvs, nsplit, st); break;
-    case 3: launch_attn_tile_g<HD, 3>(P, n, kvs, nsplit, st); break;
-    case 4: launch_attn_tile_g<HD, 4>(P, n, kvs, nsplit, st); break;
-    case 8: launch_attn_tile_g<HD, 8>(P, n, kvs, nsplit, st); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = dispatch_int<1, 2, 3, 4, 8>(gqa, [&](auto g) { launch_attn_tile_g<HD, decltype(g)::value>(P, n, kvs, nsplit, st); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_gemv_dyn(int wt, int pro, int epi, const GemvParams &P, hipStream_t st) {
@@ -775,22 +732,6 @@ hipError_t launch_gemv_dyn(int wt, int pro, int epi, const GemvParams &P, hipStr
     return hipErrorInvalidValue;
 }
 
-void push_gemv(std::vector<Op> &plan, int kind, int coll, float *buf, size_t count, int wt, int pro, int epi, const GemvParams &P) {
-    Op op{kind, coll, buf, count, nullptr};
-    op.is_gemv = true; op.wtype = wt; op.pro = pro; op.epi = epi; op.gp = P;
-    plan.push_back(op);
-}
-
-// Freeze the launch closures once every GEMV's parameters are final.
-void link_prefetch(std::vector<Op> &plan) {
-    for (Op &cur : plan) {
-        if (!cur.is_gemv) continue;
-        const int wt = cur.wtype, pro = cur.pro, epi = cur.epi;
-        const GemvParams P = cur.gp;
-        cur.fn = [wt, pro, epi, P](hipStream_t st) { return launch_gemv_dyn(wt, pro, epi, P, st); };
-    }
-}
-
 template <int WT>
 hipError_t launch_attn_block(const BlockParams &B, int npin, int grid, size_t lds, hipStream_t st) {
     if (npin == 0) hipLaunchKernelGGL((attn_block_kernel<WT, 0>), dim3(grid), dim3(BLK_THREADS), lds, st, B);
@@ -807,6 +748,66 @@ hipError_t launch_ffn_block(const FfnParams &F, int grid, hipStream_t st) {
     else hipLaunchKernelGGL((ffn_block_kernel<WT, BLK_MAX_PARTS>), dim3(grid), dim3(FFN_THREADS), lds, st, F);
     return hipGetLastError();
 }
+// mode 2's launch; nf: 256-column groups of a projection row per wavefront (1, else 2)
+hipError_t launch_qkv_attn(const GroupParams &B, int wt, int nf, int grid, hipStream_t st) {
+    const size_t lds = grp_lds_bytes();
+    if (wt == WT_Q8_0 && nf == 1) hipLaunchKernelGGL((qkv_attn_kernel<WT_Q8_0, 1>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
+    else if (wt == WT_Q8_0) hipLaunchKernelGGL((qkv_attn_kernel<WT_Q8_0, 2>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
+    else if (nf == 1) hipLaunchKernelGGL((qkv_attn_kernel<WT_Q4_0, 1>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
+    else hipLaunchKernelGGL((qkv_attn_kernel<WT_Q4_0, 2>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
+    return hipGetLastError();
+}
+template <int WT, bool MF = false, bool HELP = false>
+hipError_t launch_tp_attn_t(const TpAttnParams &Q, int nf, int grid, size_t lds, hipStream_t st) {
+    if (nf == 1) hipLaunchKernelGGL((tp_attn_kernel<WT, 1, MF, HELP>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
+    else hipLaunchKernelGGL((tp_attn_kernel<WT, 2, MF, HELP>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
+    return hipGetLastError();
+}
+// modes 3 / 4: the attention half; with helper blocks (hlp) or on the matrix pipe (mfa) the launch is Q4_0's only (nl_finalize)
+hipError_t launch_tp_attn(const TpAttnParams &Q, int wt, int nf, bool mfa, bool hlp, int grid, size_t lds, hipStream_t st) {
+    if (hlp) return launch_tp_attn_t<WT_Q4_0, false, true>(Q, nf, grid, lds, st);
+    if (mfa) return launch_tp_attn_t<WT_Q4_0, true>(Q, nf, grid, lds, st);
+    return wt == WT_Q8_0 ? launch_tp_attn_t<WT_Q8_0>(Q, nf, grid, lds, st) : launch_tp_attn_t<WT_Q4_0>(Q, nf, grid, lds, st);
+}
+template <int WT, bool MF>
+void launch_wide_ffn_t(const WideFfnParams &F, int nf, int ngc, int rounds, int grid, size_t lds, hipStream_t st) {
+    dispatch_int<1, 2>(nf == 1 ? 1 : 2, [&](auto f) {
+        dispatch_int<1, 3>(ngc <= 1 ? 1 : 3, [&](auto g) {
+            dispatch_int<1, 2, 3, 4>(std::max(1, std::min(rounds, 4)), [&](auto r) {
+                hipLaunchKernelGGL((wide_ffn_kernel<WT, decltype(f)::value, decltype(g)::value, decltype(r)::value, MF>), dim3(grid), dim3(TP_THREADS), lds, st, F);
+            });
+        });
+    });
+}
+// the feed-forward half of modes 3 / 4 as one launch; mff: Q4_0 on the matrix pipe
+hipError_t launch_wide_ffn(const WideFfnParams &F, int wt, int nf, int ngc, int rounds, bool mff, int grid, size_t lds, hipStream_t st) {
+    if (wt == WT_Q8_0) launch_wide_ffn_t<WT_Q8_0, false>(F, nf, ngc, rounds, grid, lds, st);
+    else if (mff) launch_wide_ffn_t<WT_Q4_0, true>(F, nf, ngc, rounds, grid, lds, st);
+    else launch_wide_ffn_t<WT_Q4_0, false>(F, nf, ngc, rounds, grid, lds, st);
+    return hipGetLastError();
+}
+// mode 3's feed-forward half with one-tile producers
+hipError_t launch_tp_ffn(const TpFfnParams &F, int wt, int nf, int ngc, int nr, int grid, size_t lds, hipStream_t st) {
+    dispatch_int<WT_Q8_0, WT_Q4_0>(wt == WT_Q8_0 ? WT_Q8_0 : WT_Q4_0, [&](auto w) {
+        dispatch_int<1, 2>(nf == 1 ? 1 : 2, [&](auto f) {
+            dispatch_int<1, 2>(ngc <= 1 ? 1 : 2, [&](auto g) {
+                dispatch_int<1, 2>(nr <= 1 ? 1 : 2, [&](auto r) {
+                    hipLaunchKernelGGL((tp_ffn_kernel<decltype(w)::value, decltype(f)::value, decltype(g)::value, decltype(r)::value>), dim3(grid), dim3(TP_THREADS), lds, st, F);
+                });
+            });
+        });
+    });
+    return hipGetLastError();
+}
+
+// ---- fillers: one per family of parameter structs, called from every op maker that fills that family ---------------------------
+// the words a fused launch's exchanges are tagged and given up with (BlockParams, FfnParams, GroupParams, WideFfnParams, TpFfnParams);
+// p2p: a push-group rank counts its forwards in the push seams' epoch word
+template <typename P>
+void set_sync(P &p, const nl_engine *e, int l, bool p2p) {
+    p.tick = p2p ? e->p2p.epoch : e->tick; p.layer_tag = (unsigned)(l + 1);
+    p.status = e->tick + 1; p.host_status = e->h_status; p.spin_limit = e->knobs.fused_spin_limit;
+}
 
 BlockParams attn_block_params(nl_engine *e, int l, const float *x_in) {
     const nl_config &c = e->cfg;
@@ -821,450 +822,440 @@ BlockParams attn_block_params(nl_engine *e, int l, const float *x_in) {
     B.kcache = e->kcache + (long long)l * e->kv_layer_stride; B.vcache = e->vcache + (long long)l * e->kv_layer_stride;
     B.kv_stream_stride = e->kv_stream_stride; B.ctl = e->ctl;
     B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv; B.bias_out = L.bo; B.parts = e->parts;
-    B.xchg = e->xchg; B.tick = e->tick; B.layer_tag = (unsigned)(l + 1); B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->knobs.fused_spin_limit;
+    B.xchg = e->xchg;
+    set_sync(B, e, l, false);    // (mode 1 is one GPU's, but nothing keeps nl_p2p_import from a handle of one rank: its blocks count in e->tick)
     return B;
+}
+
+// workgroups per kv group of the projection + attention launches, and the udiv_inv of 8 * members / members
+struct GroupMembers { int members; unsigned m8_inv, m_inv; };
+GroupMembers group_members(const nl_engine *e) {
+    const int m = (e->gqa + 2) * 4 / e->grp_tpm;
+    return {m, udiv_inv(8u * (unsigned)m), udiv_inv((unsigned)m)};
+}
+// 256-column groups of a projection row per wavefront of those launches (their NF)
+int group_nf(const nl_engine *e, int l) {
+    const int ngroups = (e->layers[l].qkv.npairs + KL - 1) / KL;
+    return (ngroups + 16 / e->grp_tpm - 1) / (16 / e->grp_tpm);
+}
+
+// projection + RoPE + KV store + attention of layer l on x, as mode 2 and modes 3 / 4 share it (mode 2 adds part_o / part_ml, modes
+// 3 / 4 may swap in the matrix pipe's copy of the weights)
+GroupParams group_params(nl_engine *e, int l, const float *x, bool p2p) {
+    const nl_config &c = e->cfg;
+    nl_engine::Layer &L = e->layers[l];
+    const GroupMembers gm = group_members(e);
+    GroupParams B{};
+    B.qkv_q = L.qkv.q; B.qkv_s = L.qkv.s;
+    B.D = c.dim; B.npairs = L.qkv.npairs; B.n_q_heads = e->Hs; B.n_kv_heads = e->KVs; B.seq_len = c.seq_len;
+    B.rope_conj = c.rope_conjugate; B.qk_norm = c.qk_norm; B.single_stream = c.max_streams == 1 ? 1 : 0;
+    B.tpm = e->grp_tpm; B.members = gm.members;
+    B.gqa = (unsigned)e->gqa; B.wpt = (unsigned)((GRP_THREADS / 64) / e->grp_tpm); B.wpt_inv = udiv_inv(B.wpt);
+    B.m8_inv = gm.m8_inv; B.m_inv = gm.m_inv;
+    B.x = x; B.normw = L.attn_norm; B.eps = c.rms_eps; B.scale = (float)(1.0 / std::sqrt((double)e->hd));
+    B.rope_cos = e->rope_cos; B.rope_sin = e->rope_sin;
+    B.kcache = e->kcache + (long long)l * e->kv_layer_stride; B.vcache = e->vcache + (long long)l * e->kv_layer_stride;
+    B.kv_stream_stride = e->kv_stream_stride; B.ctl = e->ctl;
+    B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv;
+    B.nsplit_max = e->nsplit_max;
+    B.xchg = e->xchg;
+    set_sync(B, e, l, p2p);
+    return B;
+}
+
+// the head TpFfnParams and WideFfnParams share
+template <typename F>
+void ffn_common(F &f, const nl_engine *e, const nl_engine::Layer &L, float *x) {
+    f.gate_q = L.gate.q; f.gate_s = L.gate.s; f.up_q = L.up.q; f.up_s = L.up.s; f.dn_q = L.down.q; f.dn_s = L.down.s;
+    f.D = e->cfg.dim; f.I = e->Is; f.npairs = L.gate.npairs; f.gu_tiles = L.gate.ntiles;
+    f.dn_npairs = L.down.npairs; f.dn_ntiles = L.down.ntiles;
+    f.normw = L.ffn_norm; f.eps = e->cfg.rms_eps; f.x = x; f.hx = e->tp_hx;
+}
+
+// L2 warm-up (nl_tp.h PfTiles) of layer N's Q | K | V tiles for a launch in front of its attention half; blocks: that launch's grid
+// (0: the tiles are only to be kept by the memory-side cache).  nmat 0 (off) where the kernels have no touch for the type.
+PfTiles pf_qkv_tiles(const nl_engine *e, const nl_engine::Layer &N, int blocks) {
+    PfTiles T{};
+    if (N.qkv.wtype != WT_Q4_0 && N.qkv.wtype != WT_Q8_0) return T;
+    T.q[0] = T.q[1] = e->mf_attn ? N.qkv.q2 : N.qkv.q; T.s[0] = T.s[1] = e->mf_attn ? N.qkv.s2 : N.qkv.s;
+    T.tile_qbytes = tile_qbytes(N.qkv.wtype, N.qkv.npairs); T.tile_sbytes = tile_sbytes(N.qkv.wtype, N.qkv.npairs);
+    T.ntiles = N.qkv.ntiles; T.nmat = 1; T.blocks = blocks;
+    return T;
+}
+
+// ---- seams: where the partial vector of a layer half goes (nl_tp.h TpSeam) -----------------------------------------------------
+// Push seams (nl_p2p.h): the partial leaves the producing launch as granules into every rank's receive slots and the same launch
+// finishes the all-reduce (each row's owner lane adds the G granules of its row to the residual stream).  Slots alternate by seam
+// parity.  Loopback (nl_p2p_loopback: one rank alone, timing only): the rank writes its partial into ALL G rank-slots of its own
+// area, so grids, stores and polls are the real ones.
+TpSeam push_seam(const nl_engine *e, int seam) {
+    const size_t slot_bytes = (size_t)e->cfg.dim * sizeof(u64);
+    TpSeam S{};
+    S.rows = e->cfg.dim;
+    for (int r = 0; r < e->G; r++)
+        S.dst[r] = reinterpret_cast<u64 *>((char *)e->p2p.peer[r] + ((size_t)(seam & 1) * e->G + (e->p2p.loopback ? r : e->rank)) * slot_bytes);
+    S.slots = reinterpret_cast<const u64 *>((char *)e->p2p.area + (size_t)(seam & 1) * e->G * slot_bytes);
+    S.n = e->G; S.epoch = e->p2p.epoch; S.seam = (unsigned)(seam + 1);
+    S.status = e->p2p.status; S.timeout = e->p2p.timeout_ticks;
+    return S;
+}
+// one GPU holds the whole layer: out[row] = resid + v
+TpSeam direct_seam(const nl_engine *e) { TpSeam S{}; S.n = -1; S.rows = e->cfg.dim; return S; }
+// a shard of an in-process group: the partial stays in `ar` for the group to sum and add (coll 3)
+TpSeam partial_seam(const nl_engine *e) { TpSeam S{}; S.n = 0; S.rows = e->cfg.dim; S.partial = e->ar; return S; }
+// the seam in the tail of a mode-3 launch
+TpSeam rank_seam(const nl_engine *e, int seam) { return e->p2p.on ? push_seam(e, seam) : partial_seam(e); }
+
+// where the partial of a WO / down GEMV goes: the residual stream in place | a push seam | `ar`, RCCL's all-reduce behind the
+// launch and the sum into the next prologue (`pending` of build_plan)
+enum class Dest { resid, push, collective };
+
+// ---- op makers: one per launch of a plan ---------------------------------------------------------------------------------------
+Op gemv_op(int kind, int coll, float *buf, size_t count, int wt, int pro, int epi, const GemvParams &P) {
+    return {kind, coll, buf, count, [wt, pro, epi, P](hipStream_t st) { return launch_gemv_dyn(wt, pro, epi, P, st); }};
+}
+
+Op embed_op(nl_engine *e, bool p2p) {
+    EmbedParams P{e->embd_raw, e->embd_type, e->cfg.dim, e->ctl, e->x[0], e->voices(), p2p ? e->p2p.epoch : e->tick};
+    e->plan_embed = P;
+    return {K_EMBED, 0, nullptr, 0, [P](hipStream_t st) {
+                hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, P);
+                return hipGetLastError();
+            }};
+}
+
+// mode 1: the whole attention half as one launch (nl_block.h); its H partial vectors are added to the residual stream by the
+// prologue of the launch behind it.  after_ffn_block: it adds the feed-forward block's partials to x_in itself and leaves x in x[0]
+Op attn_block_op(nl_engine *e, int l, const float *x_in, bool after_ffn_block) {
+    BlockParams B = attn_block_params(e, l, x_in);
+    const int npin = after_ffn_block ? e->Is / FFN_SLICE : 0;
+    if (after_ffn_block) { B.parts_in = e->parts_ffn; B.nparts_in = npin; B.x_out = e->x[0]; }
+    const int wt = e->layers[l].qkv.wtype, grid = blk_grid(e->Hs);
+    const size_t lds = blk_lds_bytes(e->cfg.dim);
+    return {K_ATTNBLOCK, 0, nullptr, 0, [B, wt, grid, lds, npin, e](hipStream_t st) mutable {
+                B.dbg = e->dbg_block;      // nl_debug_stamps only
+                return wt == WT_Q8_0 ? launch_attn_block<WT_Q8_0>(B, npin, grid, lds, st)
+                                     : launch_attn_block<WT_Q4_0>(B, npin, grid, lds, st);
+            }};
+}
+
+// mode 1 with ffn_fused: the feed-forward half as one launch, x[0] + the attention block's partials -> x[1], its own to parts_ffn
+Op ffn_block_op(nl_engine *e, int l) {
+    const nl_config &c = e->cfg;
+    nl_engine::Layer &L = e->layers[l];
+    FfnParams F{};
+    F.gate_q = L.gate.q; F.gate_s = L.gate.s; F.up_q = L.up.q; F.up_s = L.up.s; F.dn_q = L.dn_slice.q; F.dn_s = L.dn_slice.s;
+    F.D = c.dim; F.I = e->Is; F.npairs = L.gate.npairs;
+    F.x = e->x[0]; F.normw = L.ffn_norm; F.parts_in = e->parts; F.nparts_in = e->Hs; F.x_out = e->x[1]; F.eps = c.rms_eps;
+    F.parts_out = e->parts_ffn; F.xchg = e->xchg_ffn;
+    set_sync(F, e, l, false);    // (as attn_block_params)
+    const int wt = L.gate.wtype, grid = ffn_grid(e->Is / FFN_SLICE);
+    return {K_FFNBLOCK, 0, nullptr, 0, [F, wt, grid, e](hipStream_t st) mutable {
+                F.dbg = e->dbg_block;      // nl_debug_stamps only
+                return wt == WT_Q8_0 ? launch_ffn_block<WT_Q8_0>(F, grid, st) : launch_ffn_block<WT_Q4_0>(F, grid, st);
+            }};
+}
+
+// mode 2: projection + RoPE + KV store + attention as one launch (nl_group.h); WO consumes its partials
+Op group_attn_op(nl_engine *e, int l, const float *x, bool p2p) {
+    GroupParams B = group_params(e, l, x, p2p);
+    B.part_o = e->part_o; B.part_ml = e->part_ml;
+    const int wt = e->layers[l].qkv.wtype, grid = grp_grid(e->KVs, B.members), nf = group_nf(e, l);
+    return {K_ATTNBLOCK, 0, nullptr, 0, [B, wt, grid, nf](hipStream_t st) { return launch_qkv_attn(B, wt, nf, grid, st); }};
+}
+
+// nl_tp.h's attention half (projection + RoPE + KV store + attention + WO) as one op: a tensor-parallel rank's (mode 3: the seam's
+// all-reduce in its tail, or coll 3) or, with a direct seam, the whole layer's on one GPU (mode 4); help: with the helper blocks
+Op tp_attn_op(nl_engine *e, int l, float *x, const TpSeam &sm, int coll, bool p2p, bool help) {
+    const nl_config &c = e->cfg;
+    nl_engine::Layer &L = e->layers[l];
+    TpAttnParams Q{};
+    Q.G = group_params(e, l, x, p2p);
+    Q.wo_q = L.wo.q; Q.wo_s = L.wo.s; Q.wo_npairs = L.wo.npairs; Q.wo_ntiles = L.wo.ntiles; Q.wo_gshift = e->tpg.wo_gshift;
+    Q.wo_tpw = e->tpg.wo_tpw;
+    Q.n_heads_local = e->Hs; Q.xq = e->tp_xq; Q.xo = e->tp_xo; Q.bias_out = L.bo; Q.x = x;
+    Q.xp = e->tp_xp; Q.helpers = (help && e->attn_helpers) ? 1 : 0; Q.live_grid = grp_grid(e->KVs, Q.G.members);
+    Q.seam = sm;
+    const bool mfa = e->mf_attn;
+    if (mfa) { Q.G.qkv_q = L.qkv.q2; Q.G.qkv_s = L.qkv.s2; }       // (WO stays on the vector pipe: nl_tp.h)
+    if (e->wide_ffn && (e->knobs.prefetch & 1) && L.gate.wtype == L.up.wtype && (L.gate.wtype == WT_Q4_0 || L.gate.wtype == WT_Q8_0)) {
+        Q.pf.q[0] = e->mf_ffn ? L.gate.q2 : L.gate.q; Q.pf.q[1] = e->mf_ffn ? L.up.q2 : L.up.q;
+        Q.pf.s[0] = e->mf_ffn ? L.gate.s2 : L.gate.s; Q.pf.s[1] = e->mf_ffn ? L.up.s2 : L.up.s;
+        Q.pf.tile_qbytes = tile_qbytes(L.gate.wtype, L.gate.npairs); Q.pf.tile_sbytes = tile_sbytes(L.gate.wtype, L.gate.npairs);
+        Q.pf.ntiles = L.gate.ntiles; Q.pf.nmat = 2; Q.pf.blocks = L.down.ntiles; Q.pf_early = (e->knobs.prefetch & 8) ? 1 : 0;
+    }
+    if ((e->knobs.prefetch & 16) && Q.pf.nmat > 0 && l + 1 < c.n_layers) Q.pf2 = pf_qkv_tiles(e, e->layers[l + 1], 0);
+    const int wt = L.qkv.wtype, grid = std::max(Q.live_grid, (L.wo.ntiles + e->tpg.wo_tpw - 1) / e->tpg.wo_tpw), nf = group_nf(e, l);
+    const size_t lds = tp_attn_lds_bytes(L.wo.npairs);
+    const bool hlp = Q.helpers != 0;
+    Op op{K_ATTNBLOCK, coll, coll ? e->ar : nullptr, (size_t)c.dim,
+          [Q, wt, grid, nf, lds, mfa, hlp](hipStream_t st) { return launch_tp_attn(Q, wt, nf, mfa, hlp, grid, lds, st); }};
+    op.add_to = x;
+    return op;
+}
+
+// the feed-forward half of modes 3 / 4 as one launch of wide_ffn_kernel (nl_tp.h): one GPU (direct seam) or a tensor-parallel rank's
+Op wide_ffn_op(nl_engine *e, int l, float *x, const TpSeam &sm, int coll, bool p2p) {
+    const nl_config &c = e->cfg;
+    nl_engine::Layer &L = e->layers[l];
+    WideFfnParams F{};
+    ffn_common(F, e, L, x);
+    const int grid = L.down.ntiles;
+    F.rounds = (L.gate.ntiles + grid - 1) / grid;
+    set_sync(F, e, l, p2p);
+    F.seam = sm;
+    const bool mff = e->mf_ffn;
+    if (mff) { F.gate_q = L.gate.q2; F.gate_s = L.gate.s2; F.up_q = L.up.q2; F.up_s = L.up.s2; F.dn_q = L.down.q2; F.dn_s = L.down.s2; }
+    F.pf_ahead = (e->knobs.prefetch & 4) ? 1 : 0;
+    if ((e->knobs.prefetch & 2) && l + 1 < c.n_layers) {
+        const PfTiles T = pf_qkv_tiles(e, e->layers[l + 1], grid);
+        if (T.nmat) {
+            const GroupMembers gm = group_members(e);
+            PfQkv &X = F.pf;
+            X.T = T;
+            X.tpm = e->grp_tpm; X.members = gm.members; X.gqa = e->gqa; X.n_q_heads = e->Hs; X.n_kv_heads = e->KVs;
+            X.m8_inv = gm.m8_inv; X.m_inv = gm.m_inv;
+        }
+    }
+    const int wt = L.gate.wtype, nf = e->wide_nf, ngc = e->wide_ngc, rounds = F.rounds;
+    const size_t lds = wide_ffn_lds_bytes(nf, L.down.npairs);
+    Op op{K_FFNBLOCK, coll, coll ? e->ar : nullptr, (size_t)c.dim,
+          [F, wt, grid, nf, ngc, rounds, lds, mff](hipStream_t st) { return launch_wide_ffn(F, wt, nf, ngc, rounds, mff, grid, lds, st); }};
+    op.add_to = x;
+    return op;
+}
+
+// mode 3's feed-forward half where the shard's gate / up tiles fit one-tile producers (tp_ffn_kernel)
+Op tp_ffn_op(nl_engine *e, int l, float *x, const TpSeam &sm, int coll, bool p2p) {
+    nl_engine::Layer &L = e->layers[l];
+    const nl_engine::TpGeom &t = e->tpg;
+    TpFfnParams F{};
+    ffn_common(F, e, L, x);
+    F.pair = t.pair; F.n_prod = t.n_prod; F.n_cons = t.n_cons; F.ct_shift = t.ct_shift;
+    set_sync(F, e, l, p2p);
+    F.seam = sm;
+    const int wt = L.gate.wtype, grid = t.grid, nf = t.nf, ngc = t.ngc, nr = t.nr;
+    const size_t lds = tp_ffn_lds_bytes(L.down.npairs);
+    Op op{K_FFNBLOCK, coll, coll ? e->ar : nullptr, (size_t)e->cfg.dim,
+          [F, wt, grid, nf, ngc, nr, lds](hipStream_t st) { return launch_tp_ffn(F, wt, nf, ngc, nr, grid, lds, st); }};
+    op.add_to = x;
+    return op;
+}
+
+// RMSNorm + Q,K,V GEMV + RoPE + KV store (go/model.go:517-554); pending: an all-reduced partial the prologue adds to x, the sum to x_out
+Op qkv_op(nl_engine *e, int l, const float *x, const float *pending, float *x_out) {
+    const nl_config &c = e->cfg;
+    nl_engine::Layer &L = e->layers[l];
+    GemvParams P = base_params(e, L.qkv);
+    P.x = x; P.normw = L.attn_norm;
+    if (pending) { P.add = pending; P.x_out = x_out; }
+    P.rope_cos = e->rope_cos; P.rope_sin = e->rope_sin;
+    P.qbuf = e->qbuf; P.kcache = e->kcache + (long long)l * e->kv_layer_stride; P.vcache = e->vcache + (long long)l * e->kv_layer_stride;
+    P.kv_stream_stride = e->kv_stream_stride;
+    P.n_q_heads = e->Hs; P.n_kv_heads = e->KVs; P.seq_len = c.seq_len; P.rope_conj = c.rope_conjugate;
+    P.bias_q = L.bq; P.bias_k = L.bk; P.bias_v = L.bv;
+    return gemv_op(K_QKV, 0, nullptr, 0, L.qkv.wtype, PRO_NORM, EPI_QKV, P);
+}
+
+Op qknorm_op(nl_engine *e, int l) {
+    const nl_config &c = e->cfg;
+    QkNormParams P{e->qbuf, e->kcache + (long long)l * e->kv_layer_stride, e->kv_stream_stride, e->ctl, e->Hs, e->KVs, e->hd, c.seq_len, c.rms_eps};
+    const int nh = e->Hs + e->KVs;
+    return {K_QKV, 0, nullptr, 0, [P, nh](hipStream_t st) {
+                hipLaunchKernelGGL(qknorm_kernel, dim3(nh), dim3(64), 0, st, P);
+                return hipGetLastError();
+            }};
+}
+
+// GQA attention over the cache (go/model.go:557-587)
+Op attn_op(nl_engine *e, int l) {
+    const nl_config &c = e->cfg;
+    AttnParams P{e->qbuf, e->kcache + (long long)l * e->kv_layer_stride, e->vcache + (long long)l * e->kv_layer_stride,
+                 e->kv_stream_stride, e->part_o, e->part_ml, e->ctl,
+                 e->KVs, c.seq_len, e->nsplit_max, (float)(1.0 / std::sqrt((double)e->hd)), c.max_streams == 1 ? 1 : 0,
+                 nullptr, nullptr, 0, 0};
+    const dim3 grid(e->KVs, e->nsplit_max);
+    const int hd = e->hd, gqa = e->gqa;
+    return {K_ATTN, 0, nullptr, 0, [hd, gqa, P, grid](hipStream_t st) { return launch_attn(hd, gqa, P, grid, st); }};
+}
+
+// a GEMV whose rows are a partial of the residual stream x (WO, down): the one place that says where it goes
+Op partial_gemv_op(nl_engine *e, int kind, int pro, const PackedMat &m, GemvParams P, Dest dest, int seam, float *x) {
+    switch (dest) {
+    case Dest::push: {
+        const TpSeam S = push_seam(e, seam);
+        for (int r = 0; r < e->G; r++) P.p2p_dst[r] = S.dst[r];
+        P.p2p_slots = S.slots; P.p2p_n = S.n; P.p2p_epoch = S.epoch; P.p2p_seam = S.seam;
+        P.p2p_status = S.status; P.p2p_timeout = S.timeout;
+        P.out = x; P.resid = x;
+        return gemv_op(kind, 0, nullptr, 0, m.wtype, pro, EPI_P2P, P);
+    }
+    case Dest::resid:
+        P.out = x; P.resid = x;
+        return gemv_op(kind, 0, nullptr, 0, m.wtype, pro, EPI_RESID, P);
+    default:
+        P.out = e->ar;
+        return gemv_op(kind, 1, e->ar, (size_t)e->cfg.dim, m.wtype, pro, EPI_STORE, P);
+    }
+}
+
+// WO + residual (go/model.go:590-594); the prologue merges the attention splits
+Op wo_op(nl_engine *e, int l, Dest dest, int seam, float *x) {
+    nl_engine::Layer &L = e->layers[l];
+    GemvParams P = base_params(e, L.wo);
+    P.part_o = e->part_o; P.part_ml = e->part_ml;
+    P.bias_out = L.bo;
+    return partial_gemv_op(e, K_WO, PRO_ATTN, L.wo, P, dest, seam, x);
+}
+
+// RMSNorm + gate/up GEMV + SiLU*up (go/model.go:597-606).  pending: as qkv_op; parts: the prologue adds the H partial vectors of
+// mode 1's attention block to x; either way the updated residual stream goes to x_out
+Op gate_up_op(nl_engine *e, int l, const float *x, float *x_out, const float *pending, bool parts) {
+    nl_engine::Layer &L = e->layers[l];
+    GemvParams P = base_params(e, L.gate, 2);
+    P.q1 = L.up.q; P.s1 = L.up.s;
+    P.x = x; P.normw = L.ffn_norm; P.out = e->hb;
+    if (pending) { P.add = pending; P.x_out = x_out; }
+    if (parts) { P.parts = e->parts; P.nparts = e->Hs; P.x_out = x_out; }
+    return gemv_op(K_GATEUP, 0, nullptr, 0, L.gate.wtype, parts ? PRO_NORM_PARTS : PRO_NORM, EPI_SWIGLU, P);
+}
+
+// down + residual (go/model.go:609-612)
+Op down_op(nl_engine *e, int l, Dest dest, int seam, float *x) {
+    nl_engine::Layer &L = e->layers[l];
+    GemvParams P = base_params(e, L.down);
+    P.x = e->hb;
+    return partial_gemv_op(e, K_DOWN, PRO_PLAIN, L.down, P, dest, seam, x);
+}
+
+// final RMSNorm + LM head (go/model.go:616-619); tp: RCCL gathers the ranks' slices behind it (no argmax candidates, no host copy)
+Op lm_head_op(nl_engine *e, const float *x, const float *pending, float *x_out, bool tp) {
+    GemvParams P = base_params(e, e->lm_head);
+    P.x = x; P.normw = e->output_norm;
+    if (pending) { P.add = pending; P.x_out = x_out; }
+    P.out = e->logits + (size_t)e->rank * e->Vs;
+    if (!tp) { P.amax_val = e->amax_val; P.amax_idx = e->amax_idx; P.host_out = e->d_h_logits; }
+    if (e->p2p.on)   // the logits all-gather: this rank's slice also lands in every peer's gathered buffer
+        for (int r = 0; r < e->G; r++)
+            if (r != e->rank)   // (loopback: the slice fills every other rank's place in this rank's own buffer)
+                P.peer_out[r] = reinterpret_cast<float *>((char *)e->p2p.peer[r] + e->p2p.off_logits) + (size_t)(e->p2p.loopback ? r : e->rank) * e->Vs;
+    return gemv_op(K_LMHEAD, tp ? 2 : 0, e->logits, (size_t)e->Vs, e->lm_head.wtype, PRO_NORM, EPI_STORE, P);
+}
+
+// argmax candidates the LM head leaves: one per 64 rows of each of its workgroups
+int lm_head_candidates(const nl_engine *e) {
+    const GemvParams P = base_params(e, e->lm_head);
+    return ((P.ntiles + P.tw - 1) / P.tw) * ((P.tw * TR + 63) / 64);
+}
+
+Op argmax_op(nl_engine *e, bool tp) {
+    ArgmaxParams P{e->logits, e->cfg.vocab, tp ? nullptr : e->amax_val, e->amax_idx, lm_head_candidates(e), e->ctl, e->ids, e->result};
+    e->plan_argmax = P;
+    return {K_ARGMAX, 0, nullptr, 0, [P](hipStream_t st) {
+                hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, P);
+                return hipGetLastError();
+            }};
+}
+
+// a push group's argmax: every rank's best candidate to every rank
+Op p2p_argmax_op(nl_engine *e) {
+    P2PArgmaxParams P{};
+    P.A = ArgmaxParams{e->logits, e->cfg.vocab, e->amax_val, e->amax_idx, lm_head_candidates(e), e->ctl, e->ids, e->result};
+    for (int r = 0; r < e->G; r++)
+        P.dst[r] = reinterpret_cast<u64 *>((char *)e->p2p.peer[r] + e->p2p.off_amax) + 4 * (e->p2p.loopback ? r : e->rank);
+    P.slots = reinterpret_cast<const u64 *>((char *)e->p2p.area + e->p2p.off_amax);
+    // a fused-launch give-up on ANY rank travels with the pair: every rank retires its fused plan in the same call
+    if (e->tick && e->h_status) { P.fstatus = e->tick + 1; P.host_fstatus = e->h_status; }
+    P.G = e->G; P.row0 = e->rank * e->Vs; P.seam = 255u;
+    P.epoch = e->p2p.epoch; P.status = e->p2p.status; P.timeout_ticks = e->p2p.timeout_ticks;
+    e->plan_p2p_argmax = P;
+    return {K_ARGMAX, 0, nullptr, 0, [P](hipStream_t st) {
+                hipLaunchKernelGGL(p2p_argmax_kernel, dim3(1), dim3(1024), 0, st, P);
+                return hipGetLastError();
+            }};
 }
 
 // Small models at short contexts, both halves of a layer fused (nl_block.h): embed -> { attn_block -> ffn_block } x L ->
 // lm_head -> argmax, 2 launches per layer.  Each block adds its predecessor's partial vectors to the residual stream in
 // its prologue (one designated workgroup stores the sum): the feed-forward block reads x[0] and writes x[1], the
 // attention block of the next layer reads x[1] and writes x[0]; the embedding row lands in x[0].
+// (Not "mode 1 with ffn_fused" of build_plan's loop: there x alternates per prologue that takes partials in, here every block
+// writes the buffer the other kind reads, and a first attention block reads x[0] where all later ones read x[1].)
 void build_plan_blocks(nl_engine *e, std::vector<Op> &plan) {
     plan.clear();
-    const nl_config &c = e->cfg;
-    const int nslices = e->Is / FFN_SLICE;
-    {
-        EmbedParams P{e->embd_raw, e->embd_type, c.dim, e->ctl, e->x[0], e->voices(), e->tick};
-        e->plan_embed = P;
-        plan.push_back({K_EMBED, 0, nullptr, 0, [P](hipStream_t st) {
-                               hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, P);
-                               return hipGetLastError();
-                           }});
+    const int n_layers = e->cfg.n_layers;
+    plan.push_back(embed_op(e, false));
+    for (int l = 0; l < n_layers; l++) {
+        plan.push_back(attn_block_op(e, l, l == 0 ? e->x[0] : e->x[1], l > 0));
+        if (l < n_layers - 1) { plan.push_back(ffn_block_op(e, l)); continue; }
+        // last layer: gate/up and down as the two GEMV launches, so that the residual stream is complete in memory.
+        // (Measured: the feed-forward block here too, with the LM head adding the I / 256 partial vectors in its
+        // prologue -- 28 launches instead of 30 -- costs the LM head what it saves: its ~1000 workgroups each re-read
+        // seven vectors from L2, 6.5 -> 8.6 us, nano 5440 -> 5424 tok/s.)
+        plan.push_back(gate_up_op(e, l, e->x[0], e->x[1], nullptr, true));
+        plan.push_back(down_op(e, l, Dest::resid, 0, e->x[1]));
     }
-    for (int l = 0; l < c.n_layers; l++) {
-        nl_engine::Layer &L = e->layers[l];
-        {
-            BlockParams B = attn_block_params(e, l, l == 0 ? e->x[0] : e->x[1]);
-            if (l > 0) { B.parts_in = e->parts_ffn; B.nparts_in = nslices; B.x_out = e->x[0]; }
-            const int wt = L.qkv.wtype, grid = blk_grid(e->Hs), npin = l > 0 ? nslices : 0;
-            const size_t lds = blk_lds_bytes(c.dim);
-            plan.push_back({K_ATTNBLOCK, 0, nullptr, 0, [B, wt, grid, lds, npin, e](hipStream_t st) mutable {
-                                   B.dbg = e->dbg_block;      // nl_debug_stamps only
-                                   return wt == WT_Q8_0 ? launch_attn_block<WT_Q8_0>(B, npin, grid, lds, st)
-                                                        : launch_attn_block<WT_Q4_0>(B, npin, grid, lds, st);
-                               }});
-        }
-        if (l == c.n_layers - 1) {
-            // last layer: gate/up and down as the two GEMV launches, so that the residual stream is complete in memory.
-            // (Measured: the feed-forward block here too, with the LM head adding the I / 256 partial vectors in its
-            // prologue -- 28 launches instead of 30 -- costs the LM head what it saves: its ~1000 workgroups each re-read
-            // seven vectors from L2, 6.5 -> 8.6 us, nano 5440 -> 5424 tok/s.)
-            GemvParams P = base_params(e, L.gate, 2);
-            P.q1 = L.up.q; P.s1 = L.up.s;
-            P.x = e->x[0]; P.normw = L.ffn_norm; P.out = e->hb;
-            P.parts = e->parts; P.nparts = e->Hs; P.x_out = e->x[1];
-            push_gemv(plan, K_GATEUP, 0, nullptr, 0, L.gate.wtype, PRO_NORM_PARTS, EPI_SWIGLU, P);
-            GemvParams Q = base_params(e, L.down);
-            Q.x = e->hb; Q.out = e->x[1]; Q.resid = e->x[1];
-            push_gemv(plan, K_DOWN, 0, nullptr, 0, L.down.wtype, PRO_PLAIN, EPI_RESID, Q);
-        } else {
-            FfnParams F{};
-            F.gate_q = L.gate.q; F.gate_s = L.gate.s; F.up_q = L.up.q; F.up_s = L.up.s; F.dn_q = L.dn_slice.q; F.dn_s = L.dn_slice.s;
-            F.D = c.dim; F.I = e->Is; F.npairs = L.gate.npairs;
-            F.x = e->x[0]; F.normw = L.ffn_norm; F.parts_in = e->parts; F.nparts_in = e->Hs; F.x_out = e->x[1]; F.eps = c.rms_eps;
-            F.parts_out = e->parts_ffn; F.xchg = e->xchg_ffn; F.tick = e->tick; F.layer_tag = (unsigned)(l + 1);
-            F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->knobs.fused_spin_limit;
-            const int wt = L.gate.wtype, grid = ffn_grid(nslices);
-            plan.push_back({K_FFNBLOCK, 0, nullptr, 0, [F, wt, grid, e](hipStream_t st) mutable {
-                                   F.dbg = e->dbg_block;      // nl_debug_stamps only
-                                   return wt == WT_Q8_0 ? launch_ffn_block<WT_Q8_0>(F, grid, st) : launch_ffn_block<WT_Q4_0>(F, grid, st);
-                               }});
-        }
-    }
-    int lm_blocks, lm_spb;
-    {   // final RMSNorm + LM head (go/model.go:616-619)
-        GemvParams P = base_params(e, e->lm_head);
-        P.x = e->x[1]; P.normw = e->output_norm;
-        P.out = e->logits; P.amax_val = e->amax_val; P.amax_idx = e->amax_idx;
-        P.host_out = e->d_h_logits;
-        lm_blocks = (P.ntiles + P.tw - 1) / P.tw;
-        lm_spb = (P.tw * TR + 63) / 64;
-        push_gemv(plan, K_LMHEAD, 0, e->logits, (size_t)e->Vs, e->lm_head.wtype, PRO_NORM, EPI_STORE, P);
-    }
-    {
-        ArgmaxParams P{e->logits, c.vocab, e->amax_val, e->amax_idx, lm_blocks * lm_spb, e->ctl, e->ids, e->result};
-        e->plan_argmax = P;
-        plan.push_back({K_ARGMAX, 0, nullptr, 0, [P](hipStream_t st) {
-                               hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, P);
-                               return hipGetLastError();
-                           }});
-    }
-    link_prefetch(plan);
+    plan.push_back(lm_head_op(e, e->x[1], nullptr, nullptr, false));
+    plan.push_back(argmax_op(e, false));
 }
 
 // Build the per-token launch plan: the device-side restatement of Forward
 // (go/model.go:490-620).  token / pos / stream are read from e->ctl by the
-// kernels, so one captured graph serves every step.
+// kernels, so one captured graph serves every step.  The residual stream is e->x[cur]; a prologue that takes partial vectors in
+// (`pending`: the all-reduced partial of an RCCL seam; mode 1's per-head partials) leaves the sum in the other buffer.
 void build_plan(nl_engine *e, std::vector<Op> &plan, bool fused, bool help = false) {
-    if (fused && e->fused_mode == 1 && e->ffn_fused) { build_plan_blocks(e, plan); return; }
+    const int mode = fused ? e->fused_mode : 0;
+    if (mode == 1 && e->ffn_fused) { build_plan_blocks(e, plan); return; }
     plan.clear();
     const nl_config &c = e->cfg;
     const bool p2p = e->p2p.on;
     const bool tp = (e->G > 1 || e->knobs.force_tp_plan) && !p2p;   // RCCL seams (or the in-process group's own sums)
-    int cur = 0;
-    int lm_blocks = 0, lm_spb = 1;
+    const Dest dest = p2p ? Dest::push : tp ? Dest::collective : Dest::resid;
+    const int coll3 = p2p ? 0 : 3;   // mode 3 without push seams: the in-process group sums the partials in `ar` and adds them
+    int cur = 0, seam = 0;
     const float *pending = nullptr;  // all-reduced partial still to be added to the residual stream
-    // push seams (nl_p2p.h): the partial leaves the producing GEMV as granules into every rank's receive slots and the
-    // same launch finishes the all-reduce (each row's owner lane adds the G granules of its row to the residual stream,
-    // EPI_P2P).  Slots alternate by seam parity.  Loopback (nl_p2p_loopback: one rank alone, timing only): the rank
-    // writes its partial into ALL G rank-slots of its own area, so grids, stores and polls are the real ones.
-    const size_t slot_bytes = (size_t)c.dim * sizeof(u64);
-    auto p2p_producer = [&](GemvParams &P, int seam, float *x) {
-        for (int r = 0; r < e->G; r++)
-            P.p2p_dst[r] = reinterpret_cast<u64 *>((char *)e->p2p.peer[r] + ((size_t)(seam & 1) * e->G + (e->p2p.loopback ? r : e->rank)) * slot_bytes);
-        P.p2p_slots = reinterpret_cast<const u64 *>((char *)e->p2p.area + (size_t)(seam & 1) * e->G * slot_bytes);
-        P.p2p_n = e->G; P.p2p_epoch = e->p2p.epoch; P.p2p_seam = (unsigned)(seam + 1);
-        P.p2p_status = e->p2p.status; P.p2p_timeout = e->p2p.timeout_ticks;
-        P.out = x; P.resid = x;
-    };
-    int seam = 0;
+    auto flip_if_pending = [&] { if (pending) { cur ^= 1; pending = nullptr; } };
 
-    {
-        EmbedParams P{e->embd_raw, e->embd_type, c.dim, e->ctl, e->x[0], e->voices(), p2p ? e->p2p.epoch : e->tick};
-        e->plan_embed = P;
-        plan.push_back({K_EMBED, 0, nullptr, 0, [P](hipStream_t st) {
-                               hipLaunchKernelGGL(embed_kernel, dim3(1), dim3(256), 0, st, P);
-                               return hipGetLastError();
-                           }});
-    }
+    plan.push_back(embed_op(e, p2p));
     for (int l = 0; l < c.n_layers; l++) {
-        nl_engine::Layer &L = e->layers[l];
-        float *kc = e->kcache + (long long)l * e->kv_layer_stride;
-        float *vc = e->vcache + (long long)l * e->kv_layer_stride;
-        bool parts_pending = false;
-        // nl_tp.h's attention half (projection + RoPE + KV store + attention + WO) as one op: a tensor-parallel rank's (mode 3:
-        // the seam's all-reduce in its tail) or, with a direct seam, the whole layer's on one GPU (mode 4)
-        auto tp_attn_op = [&](const TpSeam &sm, int coll, float *cbuf) {
-        TpAttnParams Q{};
-        GroupParams &B = Q.G;
-        B.qkv_q = L.qkv.q; B.qkv_s = L.qkv.s;
-        B.D = c.dim; B.npairs = L.qkv.npairs; B.n_q_heads = e->Hs; B.n_kv_heads = e->KVs; B.seq_len = c.seq_len;
-        B.rope_conj = c.rope_conjugate; B.qk_norm = c.qk_norm; B.single_stream = c.max_streams == 1 ? 1 : 0;
-        B.tpm = e->grp_tpm; B.members = (e->gqa + 2) * 4 / e->grp_tpm;
-        B.gqa = (unsigned)e->gqa; B.wpt = (unsigned)((GRP_THREADS / 64) / e->grp_tpm); B.wpt_inv = udiv_inv(B.wpt);
-        B.m8_inv = udiv_inv(8u * (unsigned)B.members); B.m_inv = udiv_inv((unsigned)B.members);
-        B.x = e->x[cur]; B.normw = L.attn_norm; B.eps = c.rms_eps; B.scale = (float)(1.0 / std::sqrt((double)e->hd));
-        B.rope_cos = e->rope_cos; B.rope_sin = e->rope_sin; B.kcache = kc; B.vcache = vc;
-        B.kv_stream_stride = e->kv_stream_stride; B.ctl = e->ctl;
-        B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv;
-        B.nsplit_max = e->nsplit_max;
-        B.xchg = e->xchg; B.tick = p2p ? e->p2p.epoch : e->tick; B.layer_tag = (unsigned)(l + 1);
-        B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->knobs.fused_spin_limit;
-        Q.wo_q = L.wo.q; Q.wo_s = L.wo.s; Q.wo_npairs = L.wo.npairs; Q.wo_ntiles = L.wo.ntiles; Q.wo_gshift = e->tpg.wo_gshift;
-        Q.wo_tpw = e->tpg.wo_tpw;
-        Q.n_heads_local = e->Hs; Q.xq = e->tp_xq; Q.xo = e->tp_xo; Q.bias_out = L.bo; Q.x = e->x[cur];
-        Q.xp = e->tp_xp; Q.helpers = (help && e->attn_helpers) ? 1 : 0; Q.live_grid = grp_grid(e->KVs, B.members);
-        Q.seam = sm;
-        const bool mfa = e->mf_attn;
-        if (mfa) { B.qkv_q = L.qkv.q2; B.qkv_s = L.qkv.s2; }       // (WO stays on the vector pipe: nl_tp.h)
-        if (e->wide_ffn && (e->knobs.prefetch & 1) && L.gate.wtype == L.up.wtype && (L.gate.wtype == WT_Q4_0 || L.gate.wtype == WT_Q8_0)) {
-            Q.pf.q[0] = e->mf_ffn ? L.gate.q2 : L.gate.q; Q.pf.q[1] = e->mf_ffn ? L.up.q2 : L.up.q;
-            Q.pf.s[0] = e->mf_ffn ? L.gate.s2 : L.gate.s; Q.pf.s[1] = e->mf_ffn ? L.up.s2 : L.up.s;
-            Q.pf.tile_qbytes = tile_qbytes(L.gate.wtype, L.gate.npairs); Q.pf.tile_sbytes = tile_sbytes(L.gate.wtype, L.gate.npairs);
-            Q.pf.ntiles = L.gate.ntiles; Q.pf.nmat = 2; Q.pf.blocks = L.down.ntiles; Q.pf_early = (e->knobs.prefetch & 8) ? 1 : 0;
-        }
-        if ((e->knobs.prefetch & 16) && Q.pf.nmat > 0 && l + 1 < c.n_layers) {
-            const nl_engine::Layer &N = e->layers[l + 1];
-            if (N.qkv.wtype == WT_Q4_0 || N.qkv.wtype == WT_Q8_0) {
-                Q.pf2.q[0] = Q.pf2.q[1] = e->mf_attn ? N.qkv.q2 : N.qkv.q; Q.pf2.s[0] = Q.pf2.s[1] = e->mf_attn ? N.qkv.s2 : N.qkv.s;
-                Q.pf2.tile_qbytes = tile_qbytes(N.qkv.wtype, N.qkv.npairs); Q.pf2.tile_sbytes = tile_sbytes(N.qkv.wtype, N.qkv.npairs);
-                Q.pf2.ntiles = N.qkv.ntiles; Q.pf2.nmat = 1; Q.pf2.blocks = 0;
-            }
-        }
-        const int wt = L.qkv.wtype, grid = std::max(grp_grid(e->KVs, B.members), (L.wo.ntiles + e->tpg.wo_tpw - 1) / e->tpg.wo_tpw);
-        const int ngroups = (L.qkv.npairs + KL - 1) / KL, nf = (ngroups + 16 / e->grp_tpm - 1) / (16 / e->grp_tpm);
-        const size_t lds = tp_attn_lds_bytes(L.wo.npairs);
-        const bool hlp = Q.helpers != 0;
-        Op op{K_ATTNBLOCK, coll, cbuf, (size_t)c.dim, [Q, wt, grid, nf, lds, mfa, hlp](hipStream_t st) {
-                  if (hlp && nf == 1) hipLaunchKernelGGL((tp_attn_kernel<WT_Q4_0, 1, false, true>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else if (hlp) hipLaunchKernelGGL((tp_attn_kernel<WT_Q4_0, 2, false, true>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else if (mfa && nf == 1) hipLaunchKernelGGL((tp_attn_kernel<WT_Q4_0, 1, true>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else if (mfa) hipLaunchKernelGGL((tp_attn_kernel<WT_Q4_0, 2, true>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else if (wt == WT_Q8_0 && nf == 1) hipLaunchKernelGGL((tp_attn_kernel<WT_Q8_0, 1>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else if (wt == WT_Q8_0) hipLaunchKernelGGL((tp_attn_kernel<WT_Q8_0, 2>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else if (nf == 1) hipLaunchKernelGGL((tp_attn_kernel<WT_Q4_0, 1>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  else hipLaunchKernelGGL((tp_attn_kernel<WT_Q4_0, 2>), dim3(grid), dim3(TP_THREADS), lds, st, Q);
-                  return hipGetLastError();
-              }};
-        op.add_to = e->x[cur];
-        return op;
-        };
-        // the feed-forward half as one launch of wide_ffn_kernel (nl_tp.h): one GPU (direct seam) or a tensor-parallel rank's
-        auto wide_ffn_op = [&](const TpSeam &sm, int coll, float *cbuf) {
-        WideFfnParams F{};
-        F.gate_q = L.gate.q; F.gate_s = L.gate.s; F.up_q = L.up.q; F.up_s = L.up.s; F.dn_q = L.down.q; F.dn_s = L.down.s;
-        F.D = c.dim; F.I = e->Is; F.npairs = L.gate.npairs; F.gu_tiles = L.gate.ntiles;
-        F.dn_npairs = L.down.npairs; F.dn_ntiles = L.down.ntiles;
-        const int grid = L.down.ntiles;
-        F.rounds = (L.gate.ntiles + grid - 1) / grid;
-        F.normw = L.ffn_norm; F.eps = c.rms_eps; F.x = e->x[cur]; F.hx = e->tp_hx;
-        F.tick = p2p ? e->p2p.epoch : e->tick; F.layer_tag = (unsigned)(l + 1);
-        F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->knobs.fused_spin_limit;
-        const int wt = L.gate.wtype, nf = e->wide_nf, ngc = e->wide_ngc, rounds = F.rounds;
-        const size_t lds = wide_ffn_lds_bytes(nf, L.down.npairs);
-        F.seam = sm;
-        const bool mff = e->mf_ffn;
-        if (mff) { F.gate_q = L.gate.q2; F.gate_s = L.gate.s2; F.up_q = L.up.q2; F.up_s = L.up.s2; F.dn_q = L.down.q2; F.dn_s = L.down.s2; }
-        F.pf_ahead = (e->knobs.prefetch & 4) ? 1 : 0;
-        if ((e->knobs.prefetch & 2) && fused && (e->fused_mode == 3 || e->fused_mode == 4) && l + 1 < c.n_layers) {
-            const nl_engine::Layer &N = e->layers[l + 1];
-            if (N.qkv.wtype == WT_Q4_0 || N.qkv.wtype == WT_Q8_0) {
-                PfQkv &X = F.pf;
-                X.T.q[0] = X.T.q[1] = e->mf_attn ? N.qkv.q2 : N.qkv.q; X.T.s[0] = X.T.s[1] = e->mf_attn ? N.qkv.s2 : N.qkv.s;
-                X.T.tile_qbytes = tile_qbytes(N.qkv.wtype, N.qkv.npairs); X.T.tile_sbytes = tile_sbytes(N.qkv.wtype, N.qkv.npairs);
-                X.T.ntiles = N.qkv.ntiles; X.T.nmat = 1; X.T.blocks = grid;
-                X.tpm = e->grp_tpm; X.members = (e->gqa + 2) * 4 / e->grp_tpm; X.gqa = e->gqa; X.n_q_heads = e->Hs; X.n_kv_heads = e->KVs;
-                X.m8_inv = udiv_inv(8u * (unsigned)X.members); X.m_inv = udiv_inv((unsigned)X.members);
-            }
-        }
-        Op op{K_FFNBLOCK, coll, cbuf, (size_t)c.dim, [F, wt, grid, nf, ngc, rounds, lds, mff](hipStream_t st) {
-#define NL_WF(WT_, NF_, NGC_, R_) do { if (mff && WT_ == WT_Q4_0) hipLaunchKernelGGL((wide_ffn_kernel<WT_Q4_0, NF_, NGC_, R_, true>), dim3(grid), dim3(TP_THREADS), lds, st, F); \
-                                       else hipLaunchKernelGGL((wide_ffn_kernel<WT_, NF_, NGC_, R_>), dim3(grid), dim3(TP_THREADS), lds, st, F); } while (0)
-#define NL_WF1(WT_, NF_, NGC_) do { if (rounds <= 1) NL_WF(WT_, NF_, NGC_, 1); else if (rounds == 2) NL_WF(WT_, NF_, NGC_, 2); \
-                            else if (rounds == 3) NL_WF(WT_, NF_, NGC_, 3); else NL_WF(WT_, NF_, NGC_, 4); } while (0)
-#define NL_WF2(WT_, NF_) do { if (ngc <= 1) NL_WF1(WT_, NF_, 1); else NL_WF1(WT_, NF_, 3); } while (0)
-                               if (wt == WT_Q8_0) { if (nf == 1) NL_WF2(WT_Q8_0, 1); else NL_WF2(WT_Q8_0, 2); }
-                               else { if (nf == 1) NL_WF2(WT_Q4_0, 1); else NL_WF2(WT_Q4_0, 2); }
-#undef NL_WF2
-#undef NL_WF1
-#undef NL_WF
-                               return hipGetLastError();
-                           }};
-        op.add_to = e->x[cur];
-        return op;
-        };
-        if (fused && e->fused_mode == 3) {
+        if (mode == 3) {
             // a tensor-parallel rank's layer as two launches (nl_tp.h): both finish their all-reduce seam in the tail (push
             // path), or leave the rank's partial in `ar` for the in-process group to sum and add (coll 3)
-            auto make_seam = [&](int sm) {
-                TpSeam S{};
-                S.rows = c.dim;
-                if (p2p) {
-                    for (int r = 0; r < e->G; r++)
-                        S.dst[r] = reinterpret_cast<u64 *>((char *)e->p2p.peer[r] + ((size_t)(sm & 1) * e->G + (e->p2p.loopback ? r : e->rank)) * slot_bytes);
-                    S.slots = reinterpret_cast<const u64 *>((char *)e->p2p.area + (size_t)(sm & 1) * e->G * slot_bytes);
-                    S.n = e->G; S.epoch = e->p2p.epoch; S.seam = (unsigned)(sm + 1);
-                    S.status = e->p2p.status; S.timeout = e->p2p.timeout_ticks;
-                } else {
-                    S.n = 0; S.partial = e->ar;
-                }
-                return S;
-            };
-            {
-                plan.push_back(tp_attn_op(make_seam(seam++), p2p ? 0 : 3, p2p ? nullptr : e->ar));
-            }
-            if (e->wide_ffn) {
-                plan.push_back(wide_ffn_op(make_seam(seam++), p2p ? 0 : 3, p2p ? nullptr : e->ar));
-                continue;
-            }
-            {
-                TpFfnParams F{};
-                F.gate_q = L.gate.q; F.gate_s = L.gate.s; F.up_q = L.up.q; F.up_s = L.up.s; F.dn_q = L.down.q; F.dn_s = L.down.s;
-                F.D = c.dim; F.I = e->Is; F.npairs = L.gate.npairs; F.gu_tiles = L.gate.ntiles;
-                F.dn_npairs = L.down.npairs; F.dn_ntiles = L.down.ntiles;
-                F.pair = e->tpg.pair; F.n_prod = e->tpg.n_prod; F.n_cons = e->tpg.n_cons; F.ct_shift = e->tpg.ct_shift;
-                F.normw = L.ffn_norm; F.eps = c.rms_eps; F.x = e->x[cur]; F.hx = e->tp_hx;
-                F.tick = p2p ? e->p2p.epoch : e->tick; F.layer_tag = (unsigned)(l + 1);
-                F.status = e->tick + 1; F.host_status = e->h_status; F.spin_limit = e->knobs.fused_spin_limit;
-                F.seam = make_seam(seam++);
-                const int wt = L.gate.wtype, grid = e->tpg.grid, nf = e->tpg.nf, ngc = e->tpg.ngc, nr = e->tpg.nr;
-                const size_t lds = tp_ffn_lds_bytes(L.down.npairs);
-                Op op{K_FFNBLOCK, p2p ? 0 : 3, p2p ? nullptr : e->ar, (size_t)c.dim, [F, wt, grid, nf, ngc, nr, lds](hipStream_t st) {
-#define NL_TPF(WT_, NF_, NGC_, NR_) hipLaunchKernelGGL((tp_ffn_kernel<WT_, NF_, NGC_, NR_>), dim3(grid), dim3(TP_THREADS), lds, st, F)
-#define NL_TPF2(WT_, NF_, NGC_) do { if (nr <= 1) NL_TPF(WT_, NF_, NGC_, 1); else NL_TPF(WT_, NF_, NGC_, 2); } while (0)
-#define NL_TPF3(WT_, NF_) do { if (ngc <= 1) NL_TPF2(WT_, NF_, 1); else NL_TPF2(WT_, NF_, 2); } while (0)
-                          if (wt == WT_Q8_0) { if (nf == 1) NL_TPF3(WT_Q8_0, 1); else NL_TPF3(WT_Q8_0, 2); }
-                          else { if (nf == 1) NL_TPF3(WT_Q4_0, 1); else NL_TPF3(WT_Q4_0, 2); }
-#undef NL_TPF3
-#undef NL_TPF2
-#undef NL_TPF
-                          return hipGetLastError();
-                      }};
-                op.add_to = e->x[cur];
-                plan.push_back(op);
-            }
-            continue;
-        }
-        if (fused && e->fused_mode == 1) {
-            // the whole attention half as one launch per layer (nl_block.h); its H partial vectors are added to the
-            // residual stream by the gate/up prologue below
-            BlockParams B = attn_block_params(e, l, e->x[cur]);
-            const int wt = L.qkv.wtype, grid = blk_grid(e->Hs);
-            const size_t lds = blk_lds_bytes(c.dim);
-            plan.push_back({K_ATTNBLOCK, 0, nullptr, 0, [B, wt, grid, lds, e](hipStream_t st) mutable {
-                                   B.dbg = e->dbg_block;      // nl_debug_stamps only
-                                   return wt == WT_Q8_0 ? launch_attn_block<WT_Q8_0>(B, 0, grid, lds, st)
-                                                        : launch_attn_block<WT_Q4_0>(B, 0, grid, lds, st);
-                               }});
-            parts_pending = true;
-        } else if (fused && e->fused_mode == 4) {
+            plan.push_back(tp_attn_op(e, l, e->x[cur], rank_seam(e, seam++), coll3, p2p, help));
+            plan.push_back(e->wide_ffn ? wide_ffn_op(e, l, e->x[cur], rank_seam(e, seam++), coll3, p2p)
+                                       : tp_ffn_op(e, l, e->x[cur], rank_seam(e, seam++), coll3, p2p));
+        } else if (mode == 4 && e->wide_ffn) {
             // one GPU, wide tier: projection + RoPE + KV store + attention + WO + residual as ONE launch (nl_tp.h with a direct
-            // seam); gate / up and down follow as GEMVs on the finished residual stream
-            TpSeam S{};
-            S.n = -1; S.rows = c.dim;
-            plan.push_back(tp_attn_op(S, 0, nullptr));
-            if (e->wide_ffn) {
-                plan.push_back(wide_ffn_op(S, 0, nullptr));
-                continue;
-            }
+            // seam), the feed-forward half as another
+            plan.push_back(tp_attn_op(e, l, e->x[cur], direct_seam(e), 0, p2p, help));
+            plan.push_back(wide_ffn_op(e, l, e->x[cur], direct_seam(e), 0, p2p));
         } else {
-        if (fused && e->fused_mode == 2) {
-            // projection + RoPE + KV store + attention as one launch (nl_group.h); WO below consumes its partials
-            GroupParams B{};
-            B.qkv_q = L.qkv.q; B.qkv_s = L.qkv.s;
-            B.D = c.dim; B.npairs = L.qkv.npairs; B.n_q_heads = e->Hs; B.n_kv_heads = e->KVs; B.seq_len = c.seq_len;
-            B.rope_conj = c.rope_conjugate; B.qk_norm = c.qk_norm; B.single_stream = c.max_streams == 1 ? 1 : 0;
-            B.tpm = e->grp_tpm; B.members = (e->gqa + 2) * 4 / e->grp_tpm;
-            B.gqa = (unsigned)e->gqa; B.wpt = (unsigned)((GRP_THREADS / 64) / e->grp_tpm); B.wpt_inv = udiv_inv(B.wpt);
-            B.m8_inv = udiv_inv(8u * (unsigned)B.members); B.m_inv = udiv_inv((unsigned)B.members);
-            B.x = e->x[cur]; B.normw = L.attn_norm; B.eps = c.rms_eps; B.scale = (float)(1.0 / std::sqrt((double)e->hd));
-            B.rope_cos = e->rope_cos; B.rope_sin = e->rope_sin; B.kcache = kc; B.vcache = vc;
-            B.kv_stream_stride = e->kv_stream_stride; B.ctl = e->ctl;
-            B.bias_q = L.bq; B.bias_k = L.bk; B.bias_v = L.bv;
-            B.part_o = e->part_o; B.part_ml = e->part_ml; B.nsplit_max = e->nsplit_max;
-            B.xchg = e->xchg; B.tick = p2p ? e->p2p.epoch : e->tick; B.layer_tag = (unsigned)(l + 1);
-            B.status = e->tick + 1; B.host_status = e->h_status; B.spin_limit = e->knobs.fused_spin_limit;
-            const int wt = L.qkv.wtype, grid = grp_grid(e->KVs, B.members);
-            const int ngroups = (L.qkv.npairs + KL - 1) / KL, nf = (ngroups + 16 / e->grp_tpm - 1) / (16 / e->grp_tpm);
-            plan.push_back({K_ATTNBLOCK, 0, nullptr, 0, [B, wt, grid, nf](hipStream_t st) {
-                                   const size_t lds = grp_lds_bytes();
-                                   if (wt == WT_Q8_0 && nf == 1) hipLaunchKernelGGL((qkv_attn_kernel<WT_Q8_0, 1>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
-                                   else if (wt == WT_Q8_0) hipLaunchKernelGGL((qkv_attn_kernel<WT_Q8_0, 2>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
-                                   else if (nf == 1) hipLaunchKernelGGL((qkv_attn_kernel<WT_Q4_0, 1>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
-                                   else hipLaunchKernelGGL((qkv_attn_kernel<WT_Q4_0, 2>), dim3(grid), dim3(GRP_THREADS), lds, st, B);
-                                   return hipGetLastError();
-                               }});
-        } else {
-        {   // RMSNorm + Q,K,V GEMV + RoPE + KV store   (go/model.go:517-554)
-            GemvParams P = base_params(e, L.qkv);
-            P.x = e->x[cur]; P.normw = L.attn_norm;
-            if (pending) { P.add = pending; P.x_out = e->x[cur ^ 1]; }
-            P.rope_cos = e->rope_cos; P.rope_sin = e->rope_sin;
-            P.qbuf = e->qbuf; P.kcache = kc; P.vcache = vc; P.kv_stream_stride = e->kv_stream_stride;
-            P.n_q_heads = e->Hs; P.n_kv_heads = e->KVs; P.seq_len = c.seq_len; P.rope_conj = c.rope_conjugate;
-            P.bias_q = L.bq; P.bias_k = L.bk; P.bias_v = L.bv;
-            int wt = L.qkv.wtype;
-            push_gemv(plan, K_QKV, 0, nullptr, 0, wt, PRO_NORM, EPI_QKV, P);
-            if (pending) { cur ^= 1; pending = nullptr; }
-        }
-        if (c.qk_norm) {
-            QkNormParams P{e->qbuf, kc, e->kv_stream_stride, e->ctl, e->Hs, e->KVs, e->hd, c.seq_len, c.rms_eps};
-            int nh = e->Hs + e->KVs;
-            plan.push_back({K_QKV, 0, nullptr, 0, [P, nh](hipStream_t st) {
-                                   hipLaunchKernelGGL(qknorm_kernel, dim3(nh), dim3(64), 0, st, P);
-                                   return hipGetLastError();
-                               }});
-        }
-        {   // GQA attention over the cache (go/model.go:557-587)
-            AttnParams P{e->qbuf, kc, vc, e->kv_stream_stride, e->part_o, e->part_ml, e->ctl,
-                         e->KVs, c.seq_len, e->nsplit_max, (float)(1.0 / std::sqrt((double)e->hd)), c.max_streams == 1 ? 1 : 0,
-                         nullptr, nullptr, 0, 0};
-            dim3 grid(e->KVs, e->nsplit_max);
-            int hd = e->hd, gqa = e->gqa;
-            plan.push_back({K_ATTN, 0, nullptr, 0,
-                               [hd, gqa, P, grid](hipStream_t st) { return launch_attn(hd, gqa, P, grid, st); }});
-        }
-        }   // five-launch projection / attention
-        {   // WO + residual (go/model.go:590-594); the prologue merges the attention splits
-            GemvParams P = base_params(e, L.wo);
-            P.part_o = e->part_o; P.part_ml = e->part_ml;
-            P.bias_out = L.bo;
-            int wt = L.wo.wtype;
-            if (p2p) {
-                p2p_producer(P, seam++, e->x[cur]);
-                push_gemv(plan, K_WO, 0, nullptr, 0, wt, PRO_ATTN, EPI_P2P, P);
-            } else if (!tp) {
-                P.out = e->x[cur]; P.resid = e->x[cur];
-                push_gemv(plan, K_WO, 0, nullptr, 0, wt, PRO_ATTN, EPI_RESID, P);
-            } else {
-                P.out = e->ar;
-                push_gemv(plan, K_WO, 1, e->ar, (size_t)c.dim, wt, PRO_ATTN, EPI_STORE, P);
-                pending = e->ar;
+            // the attention half: one launch (modes 1, 4), projection + attention and WO (mode 2), or the five-launch plan's four
+            if (mode == 1) plan.push_back(attn_block_op(e, l, e->x[cur], false));
+            else if (mode == 4) plan.push_back(tp_attn_op(e, l, e->x[cur], direct_seam(e), 0, p2p, help));
+            else {
+                if (mode == 2) plan.push_back(group_attn_op(e, l, e->x[cur], p2p));
+                else {
+                    plan.push_back(qkv_op(e, l, e->x[cur], pending, e->x[cur ^ 1]));
+                    flip_if_pending();
+                    if (c.qk_norm) plan.push_back(qknorm_op(e, l));
+                    plan.push_back(attn_op(e, l));
+                }
+                plan.push_back(wo_op(e, l, dest, seam, e->x[cur]));
+                if (dest == Dest::push) seam++;
+                if (dest == Dest::collective) pending = e->ar;
             }
-        }
-        }   // !fused
-        {   // RMSNorm + gate/up GEMV + SiLU*up (go/model.go:597-606)
-            GemvParams P = base_params(e, L.gate, 2);
-            P.q1 = L.up.q; P.s1 = L.up.s;
-            P.x = e->x[cur]; P.normw = L.ffn_norm; P.out = e->hb;
-            if (pending) { P.add = pending; P.x_out = e->x[cur ^ 1]; }
-            int wt = L.gate.wtype;
-            if (parts_pending) {
-                P.parts = e->parts; P.nparts = e->Hs; P.x_out = e->x[cur ^ 1];
-                push_gemv(plan, K_GATEUP, 0, nullptr, 0, wt, PRO_NORM_PARTS, EPI_SWIGLU, P);
-                cur ^= 1;
-            } else {
-                push_gemv(plan, K_GATEUP, 0, nullptr, 0, wt, PRO_NORM, EPI_SWIGLU, P);
-            }
-            if (pending) { cur ^= 1; pending = nullptr; }
-        }
-        {   // down + residual (go/model.go:609-612)
-            GemvParams P = base_params(e, L.down);
-            P.x = e->hb;
-            int wt = L.down.wtype;
-            if (p2p) {
-                p2p_producer(P, seam++, e->x[cur]);
-                push_gemv(plan, K_DOWN, 0, nullptr, 0, wt, PRO_PLAIN, EPI_P2P, P);
-            } else if (!tp) {
-                P.out = e->x[cur]; P.resid = e->x[cur];
-                push_gemv(plan, K_DOWN, 0, nullptr, 0, wt, PRO_PLAIN, EPI_RESID, P);
-            } else {
-                P.out = e->ar;
-                push_gemv(plan, K_DOWN, 1, e->ar, (size_t)c.dim, wt, PRO_PLAIN, EPI_STORE, P);
-                pending = e->ar;
-            }
+            // gate / up and down as GEMVs; behind mode 1's block gate / up adds its partials to the residual stream
+            plan.push_back(gate_up_op(e, l, e->x[cur], e->x[cur ^ 1], pending, mode == 1));
+            if (mode == 1) cur ^= 1;
+            flip_if_pending();
+            plan.push_back(down_op(e, l, dest, seam, e->x[cur]));
+            if (dest == Dest::push) seam++;
+            if (dest == Dest::collective) pending = e->ar;
         }
     }
-    {   // final RMSNorm + LM head (go/model.go:616-619)
-        GemvParams P = base_params(e, e->lm_head);
-        P.x = e->x[cur]; P.normw = e->output_norm;
-        if (pending) { P.add = pending; P.x_out = e->x[cur ^ 1]; }
-        P.out = e->logits + (size_t)e->rank * e->Vs;
-        if (!tp) { P.amax_val = e->amax_val; P.amax_idx = e->amax_idx; P.host_out = e->d_h_logits; }
-        if (p2p)   // the logits all-gather: this rank's slice also lands in every peer's gathered buffer
-            for (int r = 0; r < e->G; r++)
-                if (r != e->rank)   // (loopback: the slice fills every other rank's place in this rank's own buffer)
-                    P.peer_out[r] = reinterpret_cast<float *>((char *)e->p2p.peer[r] + e->p2p.off_logits) + (size_t)(e->p2p.loopback ? r : e->rank) * e->Vs;
-        int wt = e->lm_head.wtype;
-        lm_blocks = (P.ntiles + P.tw - 1) / P.tw;
-        lm_spb = (P.tw * TR + 63) / 64;
-        push_gemv(plan, K_LMHEAD, tp ? 2 : 0, e->logits, (size_t)e->Vs, wt, PRO_NORM, EPI_STORE, P);
-    }
-    if (p2p) {
-        P2PArgmaxParams P{};
-        P.A = ArgmaxParams{e->logits, c.vocab, e->amax_val, e->amax_idx, lm_blocks * lm_spb, e->ctl, e->ids, e->result};
-        for (int r = 0; r < e->G; r++)
-            P.dst[r] = reinterpret_cast<u64 *>((char *)e->p2p.peer[r] + e->p2p.off_amax) + 4 * (e->p2p.loopback ? r : e->rank);
-        P.slots = reinterpret_cast<const u64 *>((char *)e->p2p.area + e->p2p.off_amax);
-        // a fused-launch give-up on ANY rank travels with the pair: every rank retires its fused plan in the same call
-        if (e->tick && e->h_status) { P.fstatus = e->tick + 1; P.host_fstatus = e->h_status; }
-        P.G = e->G; P.row0 = e->rank * e->Vs; P.seam = 255u;
-        P.epoch = e->p2p.epoch; P.status = e->p2p.status; P.timeout_ticks = e->p2p.timeout_ticks;
-        e->plan_p2p_argmax = P;
-        plan.push_back({K_ARGMAX, 0, nullptr, 0, [P](hipStream_t st) {
-                               hipLaunchKernelGGL(p2p_argmax_kernel, dim3(1), dim3(1024), 0, st, P);
-                               return hipGetLastError();
-                           }});
-    } else {
-        ArgmaxParams P{e->logits, c.vocab, tp ? nullptr : e->amax_val, e->amax_idx, lm_blocks * lm_spb, e->ctl, e->ids,
-                       e->result};
-        e->plan_argmax = P;
-        plan.push_back({K_ARGMAX, 0, nullptr, 0, [P](hipStream_t st) {
-                               hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, P);
-                               return hipGetLastError();
-                           }});
-    }
-    link_prefetch(plan);
+    plan.push_back(lm_head_op(e, e->x[cur], pending, e->x[cur ^ 1], tp));
+    plan.push_back(p2p ? p2p_argmax_op(e) : argmax_op(e, tp));
 }
 
 int run_collective(nl_engine *e, const Op &op) {
@@ -2304,8 +2295,8 @@ int batched_step(nl_engine *e, nl_engine::Batch &b, hipStream_t st, int n, int l
                 P.fin_xf = b.xfrag; P.fin_nt16 = nt16; P.fin_q4 = L.wo.wtype == WT_Q4_0 ? 1 : 0;
                 if (rope_in_attn)
                     P.rp = AttnParams::Rope{1, qkv_out, (int)R, e->Hs, c.rope_conjugate, e->rope_cos, e->rope_sin, L.bq, L.bk, L.bv, kc, vc};
-                LCK(hd == 64 ? launch_attn_fin_hd<64>(e->gqa, P, dim3(e->KVs, 1, n), st)
-                             : launch_attn_fin_hd<32>(e->gqa, P, dim3(e->KVs, 1, n), st));
+                LCK((hd == 64 ? launch_attn_hd<64, true, true>(e->gqa, P, dim3(e->KVs, 1, n), st)
+                              : launch_attn_hd<32, true, true>(e->gqa, P, dim3(e->KVs, 1, n), st)));
                 merged = true;
             } else {
                 if (rope_in_attn)

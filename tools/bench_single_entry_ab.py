@@ -1,14 +1,16 @@
 """Developer tool: A/B of two builds of libnanollama_hip.so on the host side of the single-stream entry points -- per-call forward
 with logits and forward_argmax on the resident session, forward_argmax on the one-step persistent launch (NL_PERSIST_SESSION=0) and
 on the call box (NL_PERSIST=0), decode_greedy and sample_decode of 256 tokens -- nano Q8_0, wall clock per call, and bench.py's
-headline.  The builds alternate (NL_LIB_PATH), the first of a round changing every round; per row and build the median of the
+headline; and of the launch plans' closures, which the host runs wherever no graph replays them: forward_argmax with eager launches
+(NL_PERSIST=0 NL_NO_GRAPH=1), a step of the in-process shard group on the two-launch rank plan (LocalTPGroup(fused=True), tp 2, a
+three-layer D 1024 Q4_0 model), and load_llama_model itself (plan building and graph capture).  The builds alternate (NL_LIB_PATH), the first of a round changing every round; per row and build the median of the
 rounds and their min..max; the bar a change of host code is held to: its median inside the other build's min..max.
 
     python tools/bench_single_entry_ab.py PARENT.so PR.so [rounds=5]    # the table
     python tools/bench_single_entry_ab.py rows                          # one build's rows (what the driver starts per round)
 
 rows: per-call rows 3 windows of 1000 calls (positions 8 .. 1007 of a reset stream) after a warm-up window, chains 3 windows of 8
-calls; the median window."""
+calls, group steps 3 windows of 300 (positions 0 .. 299), loads 3 after a first; the median window."""
 import json, os, re, statistics, subprocess, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,6 +51,7 @@ def rows():
              ("forward_argmax, one-step persistent launch", {"NL_PERSIST_SESSION": "0"}, lambda d: per_call(d, d.forward_argmax)),
              ("forward_argmax, call box", {"NL_PERSIST": "0"}, lambda d: per_call(d, d.forward_argmax)),
              ("forward with logits, call box", {"NL_PERSIST": "0"}, lambda d: per_call(d, d.forward)),
+             ("forward_argmax, eager launch plans", {"NL_PERSIST": "0", "NL_NO_GRAPH": "1"}, lambda d: per_call(d, d.forward_argmax)),
              ("decode_greedy x 256", {}, lambda d: chain(d, lambda: d.decode_greedy(toks[8], 8, 256))),
              ("decode_greedy x 256, launch plans", {"NL_PERSIST": "0"}, lambda d: chain(d, lambda: d.decode_greedy(toks[8], 8, 256))),
              ("sample_decode x 256", {}, lambda d: chain(d, lambda: d.sample_decode(8, 256, uniforms=us, recent=[], **SETTINGS)))]
@@ -65,6 +68,36 @@ def rows():
         if dev.last_error():
             print("NOTE", name, dev.last_error(), flush=True)
         dev.close()
+
+    def row(name, window):
+        window()
+        runs = sorted(window() for _ in range(3))
+        print(f"ROW {name}: {runs[1]:.4f} ms", flush=True)
+
+    from nanollama_amd import gguf, synth
+    shape = synth.ModelShape("ab_tp2", 3, 1024, 16, 4, 4096, seq_len=320, interm=2048)      # gqa4 of tests/test_gpu_tp_fused.py
+    path = "/tmp/nl_ab_tp2_q4_0.gguf"
+    if not os.path.exists(path):
+        synth.generate_gguf(path, shape, "q4_0", 1004, mode="qrand")
+    grp = model.LocalTPGroup(gguf.load_gguf(path), 2, fused=True)
+
+    def group_window():
+        t0 = time.perf_counter()
+        for pos in range(300):
+            grp.forward(toks[pos] % shape.vocab, pos)
+        return (time.perf_counter() - t0) / 300 * 1e3
+    row("LocalTPGroup(fused=True) step, tp 2", group_window)
+    if grp.shards[0].plan_info()["fused_mode"] != 3 or grp.shards[0].last_error():
+        print("NOTE group", grp.shards[0].plan_info(), grp.shards[0].last_error(), flush=True)
+    grp.close()
+
+    def load_window():
+        t0 = time.perf_counter()
+        dev = model.load_llama_model(g)
+        dt = time.perf_counter() - t0
+        dev.close()
+        return dt * 1e3
+    row("load_llama_model, nano q8_0", load_window)
 
 
 def main():

@@ -18,7 +18,9 @@ quantisation is part of the model and not of the error.  The two float32 constan
 the model in the same way: the cos/sin tables ((float)cos(angle), go/model.go:346-358) and the score scale (float)(1/sqrt(hd)).
 
 tests/test_attn_cases_cpu.py pins the generator (the oracle stays within REF_CAP of forward_f64 on every case, and the cases
-do contain the rows they exist for); tests/test_gpu_attention_sharp.py holds every attention kernel to forward_f64.
+do contain the rows they exist for); tests/test_gpu_attention_sharp.py holds every attention kernel to forward_f64, and
+tests/test_gpu_attention_geometry.py every (head_dim, GQA group) instantiation of them (GEO below).  What the two GPU files share
+-- the bound, the witnesses, the batch layouts, the mixed steps -- stands at the end of this module.
 """
 from __future__ import annotations
 
@@ -49,7 +51,21 @@ SHAPES: Dict[str, synth.ModelShape] = {
     "wide": synth.ModelShape("sh_wide", 2, 1024, 16, 4, 512, seq_len=192, interm=1024),  # the projection + attention launch's tier
 }
 
-# (shape, weight type, case): exactly the models the GPU file uses; test_attn_cases_cpu.py runs every one of them
+# One shape per attention geometry nl_create admits -- head_dim 32 / 64 x 1, 2, 3, 4, 6, 8 query heads per kv head; every attention
+# kernel is a template over that pair.  The smallest models that still have two kv heads (a wrong kv-head index shows):
+# D = hd * 2G, H = 2G.  (64, 2) is "gqa" and (32, 3) is "hd32_g3" above; the other ten are geo_{hd}_{g}.
+GEOMETRIES: List[Tuple[int, int]] = [(hd, g) for hd in (32, 64) for g in (1, 2, 3, 4, 6, 8)]
+GEO: Dict[Tuple[int, int], str] = {}
+for _hd, _g in GEOMETRIES:
+    _have = [k for k, s in SHAPES.items() if (s.dim, s.n_head, s.n_kv_head, s.seq_len) == (_hd * 2 * _g, 2 * _g, 2, 320)
+             and not s.attn_bias and not s.rope_conjugate]
+    GEO[_hd, _g] = _have[0] if _have else f"geo_{_hd}_{_g}"
+    if not _have:
+        SHAPES[GEO[_hd, _g]] = synth.ModelShape(f"geo_{_hd}_{_g}", 2, _hd * 2 * _g, 2 * _g, 2, 512, seq_len=320, interm=256)
+# q4_0 where D is a whole number of 256-column groups: those steps go through dgemm_kernel's RoPE epilogue
+GEO_Q4 = [(hd, g) for hd, g in GEOMETRIES if (hd * 2 * g) % 256 == 0]
+
+# (shape, weight type, case): exactly the models the GPU files use; test_attn_cases_cpu.py runs every one of them
 CASES: List[Tuple[str, str, str]] = (
     [("gqa", "q8_0", c) for c in ("sharp", "self", "anti")] + [("gqa", "q4_0", "sharp")]
     + [("gqa", "f16", c) for c in ("sharp", "self", "anti")]
@@ -59,6 +75,11 @@ CASES: List[Tuple[str, str, str]] = (
     + [("mha3", "q8_0", c) for c in ("sharp", "self", "anti")]
     + [("hd32_g3", "q8_0", "sharp")]
     + [("wide", "q4_0", c) for c in ("sharp", "self", "anti")])
+# the geometry grid (tests/test_gpu_attention_geometry.py): sharp and anti -- the case in which a split's merge weight underflows --
+# at q8_0 for all twelve, sharp at q4_0 for GEO_Q4.  (The (64, 2) and (32, 3) ones partly stand above already.)
+for _c in ([(GEO[k], "q8_0", c) for k in GEOMETRIES for c in ("sharp", "anti")] + [(GEO[k], "q4_0", "sharp") for k in GEO_Q4]):
+    if _c not in CASES:
+        CASES.append(_c)
 
 SEED = 8101
 
@@ -286,3 +307,201 @@ def coverage(run: F64Run, steps=None) -> Dict[str, int]:
             "max_in_last_split_at_pos_ge_256": int((late & (am // SPLIT == pos // SPLIT)).sum()),
             "max_is_newest_key": int((am == pos).sum()),
             "split_weight_underflows": int((np.nan_to_num(gap, nan=0.0).min(axis=-1) < -88.0).sum())}
+
+
+# ------------------------------------------------------------------- what the GPU files share: bounds, witnesses, layouts ---
+# (tests/test_gpu_attention_sharp.py, tests/test_gpu_attention_geometry.py and the latter's child, tests/attn_geometry_worker.py.
+#  `model` below is nanollama_amd.model: this module itself never loads the HIP library.)
+
+KV_TOL = 2e-5          # single ops, DESIGN section 5: |d| <= 2e-5 * (1 + |v|)
+
+_cases: Dict[Tuple[str, str, str], tuple] = {}
+
+
+def cached_case(mkdir, key: Tuple[str, str, str]):
+    """(loaded GGUF, token sequence, F64Model, float64 run over the sequence) of a (shape, weight type, case), built once per
+    process; mkdir() returns a fresh directory for the file"""
+    key = tuple(key)
+    assert key in CASES, f"{key} is not pinned by test_attn_cases_cpu.py"
+    if key not in _cases:
+        g = build_case(os.path.join(str(mkdir()), "m.gguf"), *key)
+        toks = tokens(key[0])
+        _cases[key] = (g, toks, F64Model(g), forward_f64(g, toks))
+    return _cases[key]
+
+
+class Worst:
+    """the largest max|gpu - f64| / max(1, std) of a test, and where"""
+
+    def __init__(self, what):
+        self.what, self.err, self.at = what, 0.0, None
+
+    def see(self, got, want64, at):
+        e = rel_err(got, want64)
+        if e > self.err:
+            self.err, self.at = e, at
+        return e
+
+    def line(self, run=None):
+        note = ""
+        if run is not None and isinstance(self.at, int):
+            note = f", smallest top-two margin of that step {float(run.top2_gap[self.at].min()):.2f} nats"
+        return f"{self.what}: max|gpu-f64|/max(1,std) = {self.err:.2e} (at {self.at}{note})"
+
+    def close(self, run=None):
+        print("\n" + self.line(run))
+        assert self.err <= GPU_TOL, (self.what, self.err, self.at)
+
+
+def kinds(dev, pos):
+    """the launch kinds of the single-token step at `pos` and how many of each"""
+    return {k: c for k, (ms, c) in dev.profile_forward(5, pos, iters=1).items() if c}
+
+
+def teacher_forced(dev, toks, run, w):
+    for pos, t in enumerate(toks):
+        dev.forward(t, pos)
+        w.see(dev.state.logits, run.logits[pos], pos)
+
+
+# Decode batches: five streams at ragged positions, five steps each.  A step's attention grid has as many 128-key splits as its
+# deepest row needs (batched_step, nl_engine.hip), and the engine rotates q / k inside the attention launch (attn_rope_prologue,
+# which also adds the biases and stores the K / V rows) only while that is at most two and the Q|K|V GEMM is the plain one (Q8_0 /
+# F16 files; a Q4_0 file's short steps go to dgemm_kernel, which rotates in its own epilogue):
+#   one_split     every position below 128: attn_kernel<FIN> writes the WO fragments itself, no merge launch;  NL_ROPE_IN_ATTN acts
+#   two_splits    positions 3 .. 204, two streams cross 128: items + battn_merge_kernel over two partials;      NL_ROPE_IN_ATTN acts
+#   three_splits  positions 3 .. 294, straddling 128 and 256: items + battn_merge_kernel over three partials; the knob is inert (the
+#                 brope_kv launch rotates whatever it says), both values run because the step graph is keyed on it
+BATCH_STARTS = {"one_split": [0, 3, 60, 100, 122], "two_splits": [3, 100, 124, 126, 200], "three_splits": [3, 125, 127, 254, 290]}
+BATCH_STEPS = 5
+BATCH_BELOW = {"one_split": 128, "two_splits": 256, "three_splits": 300}
+
+
+def batch_run(dev, toks, start) -> np.ndarray:
+    """BATCH_STEPS decode steps of len(start) streams that stand at `start` (prefilled here): logits [step, stream, vocab]"""
+    ns = len(start)
+    for s in range(ns):
+        if start[s]:
+            dev.prefill(toks[:start[s]], stream=s, want_logits=False)
+    out = []
+    for k in range(BATCH_STEPS):
+        pos = [start[s] + k for s in range(ns)]
+        ids, lg = dev.forward_batch(list(range(ns)), [toks[p] for p in pos], pos, want_logits=True)
+        out.append(lg.copy())
+    return np.stack(out)
+
+
+def batch_see(w: Worst, out: np.ndarray, run: F64Run, start) -> None:
+    for k in range(BATCH_STEPS):
+        for s in range(len(start)):
+            w.see(out[k, s], run.logits[start[s] + k], start[s] + k)
+
+
+PROMPT_PREFIXES = (130, 257, 300)      # a prompt's logits are its last row's: three prefixes
+
+
+def prompt_run(dev, g: gguf.GGUFFile, toks, run: F64Run, w: Worst, what: str):
+    """prefill every prefix of PROMPT_PREFIXES on `dev` (logits of the last row into `w`), then read the K / V rows of all 300
+    positions: ({prefix: logits}, {"k_cache" | "v_cache": rows}, the worst |gpu - f64| / (1 + |v|) of the rows)"""
+    m = g.meta
+    hd, S = m.head_dim, m.seq_len
+    nkv = m.num_layers * m.num_kv_heads * S * hd
+    last, cache, kv_worst = {}, {}, 0.0
+    for n in PROMPT_PREFIXES:
+        dev.reset()
+        dev.prefill(toks[:n])
+        last[n] = dev.state.logits.copy()
+        w.see(last[n], run.logits[n - 1], n - 1)
+    for which, want in (("k_cache", run.k), ("v_cache", run.v)):
+        got = dev.debug_read(which, nkv).reshape(m.num_layers, m.num_kv_heads, S, hd)[:, :, :PROMPT_PREFIXES[-1]]
+        cache[which] = got
+        d = float((np.abs(got.astype(np.float64) - want) / (1.0 + np.abs(want))).max())
+        print(f"\n{which} {what}: max|gpu-f64|/(1+|v|) = {d:.2e}")
+        kv_worst = max(kv_worst, d)
+    return last, cache, kv_worst
+
+
+def mixed_steps(toks, chunk):
+    """a 200-token prompt (stream 2) beside two decode rows that stand at 130 and 260.  chunk 199: ONE step carries the whole
+    prompt -- a single segment of 199 rows (seven query tiles of 32, tiles that straddle key 128) and its final token as an output
+    row; chunk 64: the same prompt admitted as 64 / 64 / 64 / 7 rows (segments that start at a position > 0, a short last one)."""
+    steps, a, b = [], 130, 260
+    bounds = [(p0, min(p0 + chunk, 199)) for p0 in range(0, 199, chunk)]
+    for k, (p0, p1) in enumerate(bounds):
+        out = [(0, a + k), (1, b + k)] + ([(2, 199)] if p1 == 199 else [])      # the final prompt token joins as an output row
+        rows = out + [(2, p) for p in range(p0, p1)]
+        steps.append(([s for s, _ in rows], [toks[p] for _, p in rows], [p for _, p in rows], len(out)))
+    k = len(bounds)
+    steps.append(([0, 1, 2], [toks[a + k], toks[b + k], toks[200]], [a + k, b + k, 200], 3))   # a decode step over the chunk's K / V
+    return steps
+
+
+def mixed_run(model, g, toks, chunk, knob, monkeypatch):
+    """the steps of mixed_steps on a fresh handle: (logits of the output rows per step, their positions)"""
+    monkeypatch.setenv("NL_MIXED_ATTN", knob)
+    dev = model.load_llama_model(g, max_streams=3)
+    dev.prefill(toks[:130], stream=0, want_logits=False)
+    dev.prefill(toks[:260], stream=1, want_logits=False)
+    got = []
+    for streams, tk, pos, n_out in mixed_steps(toks, chunk):
+        ids, lg = dev.forward_mixed(streams, tk, pos, n_out, want_logits=True)
+        got.append((lg.copy(), pos[:n_out]))
+    dev.close()
+    return got
+
+
+class PlacementMiss(Exception):
+    pass
+
+
+def no_warning(dev):
+    err = dev.last_error()
+    if "not placed 32 per XCD" in err:       # a property of the moment on the device (nl_persist.h): the chunk was redone on the
+        raise PlacementMiss(err)             # launch plans, so the run did not test the persistent path
+    return err == ""
+
+
+def persistent_run(model, g, toks, f64, run, what):
+    """the persistent decode (pd_decode_kernel) over the case: the resident session teacher-forced, then a chained greedy run"""
+    dev = model.load_llama_model(g)
+    try:
+        info = dev.persist_info()
+        assert info["ready"] and info["max_pos"] == 320, info
+        # (a) the resident session: per-call Forward over the whole sequence, passes of 128 keys from position 128 and 256 on
+        w = Worst(f"persistent decode, resident session {what}")
+        teacher_forced(dev, toks, run, w)
+        info = dev.persist_info()          # (one resident launch unless the host paused longer than the idle limit)
+        assert no_warning(dev) and info["tokens"] == len(toks) and 1 <= info["launches"] <= 4, info
+        # (b) chained greedy steps at positions 100 .. 159: below 128 a head's single record, above it the merge of the records
+        # in LDS.  The device picks its own tokens; the float64 forward is fed the ids it produced.
+        dev.reset()
+        n0, steps = PERSIST_PROMPT, PERSIST_STEPS
+        dev.prefill(toks[:n0])
+        tok = int(np.argmax(dev.state.logits))
+        fed, rows = [], []
+        for i in range(steps):
+            fed.append(tok)
+            (tok,) = dev.decode_greedy(tok, n0 + i, 1)
+            rows.append(dev.debug_read("logits", g.meta.vocab_size))
+        info2 = dev.persist_info()
+        assert no_warning(dev) and info2["tokens"] - info["tokens"] == steps, (info, info2)
+    finally:
+        dev.close()
+    seq = list(toks[:n0]) + fed
+    want = f64.forward(seq)
+    # the inputs' condition on the sequence the device chose (test_attn_cases_cpu.py pins it on the oracle's own chain): the CPU
+    # oracle, teacher-forced with the device's ids, stays within REF_CAP of float64 there too
+    errs, oracle_ids = oracle_errs(g, seq, want)
+    picked = fed[1:] + [tok]                                         # the id the device chose at positions n0 .. n0 + steps - 1
+    same = sum(picked[i] == oracle_ids[n0 + i] for i in range(steps))
+    print(f"\npersistent decode, greedy chain {what}: max|oracle-f64| on the device's ids = {max(errs):.2e}; "
+          f"{same} of {steps} device ids are the oracle's (all: the device followed the oracle's own chain)")
+    assert max(errs) <= REF_CAP, max(errs)
+    wg = Worst(f"persistent decode, greedy chain {what}")
+    for i in range(steps):
+        wg.see(rows[i], want.logits[n0 + i], n0 + i)
+    if what.endswith("/self"):             # on the ids the device chose the newest key still wins every row
+        cov = coverage(want, range(n0, n0 + steps))
+        assert cov["max_is_newest_key"] == cov["rows"], cov
+    w.close(run)
+    wg.close(want)

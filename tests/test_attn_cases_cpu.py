@@ -1,4 +1,5 @@
-"""Pins tests/attn_cases.py (no GPU): for every (shape, weight type, case) tests/test_gpu_attention_sharp.py uses,
+"""Pins tests/attn_cases.py (no GPU): for every (shape, weight type, case) tests/test_gpu_attention_sharp.py and
+tests/test_gpu_attention_geometry.py use,
 (a) the CPU oracle stays within REF_CAP = 5e-5 of the float64 forward at every step of the token sequence -- half the project's
     logits tolerance, so a GPU failure against float64 cannot be the input's fault.  The cap is a condition on the inputs, not
     a measurement: a case that breaks it gets a lower sigma, never a higher cap;

@@ -20,9 +20,12 @@ import attn_cases as ac  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 TOL = ac.GPU_TOL
-KV_TOL = 2e-5            # single ops, DESIGN section 5: |d| <= 2e-5 * (1 + |v|)
+KV_TOL = ac.KV_TOL       # single ops, DESIGN section 5: |d| <= 2e-5 * (1 + |v|)
 THREE = ("sharp", "self", "anti")
 SHIFT = ("shift_pos", "shift_neg")
+# the bound, the witnesses and the layouts live beside forward_f64: tests/test_gpu_attention_geometry.py runs them over every
+# (head_dim, GQA group) instantiation
+Worst, _kinds, _teacher_forced = ac.Worst, ac.kinds, ac.teacher_forced
 
 
 @pytest.fixture(scope="module")
@@ -33,52 +36,12 @@ def hip():
     return model
 
 
-_cases = {}
-
-
 @pytest.fixture(scope="module")
 def case(tmp_path_factory):
-    """(loaded GGUF, token sequence, float64 run over it) of a (shape, weight type, case): built once per module"""
+    """(loaded GGUF, token sequence, float64 run over it) of a (shape, weight type, case): built once per session"""
     def get(shape_key, wtype, name):
-        key = (shape_key, wtype, name)
-        assert key in ac.CASES, f"{key} is not pinned by test_attn_cases_cpu.py"
-        if key not in _cases:
-            g = ac.build_case(str(tmp_path_factory.mktemp("sharp") / "m.gguf"), shape_key, wtype, name)
-            toks = ac.tokens(shape_key)
-            _cases[key] = (g, toks, ac.F64Model(g), ac.forward_f64(g, toks))
-        g, toks, f64, run = _cases[key]
-        return g, toks, f64, run
+        return ac.cached_case(lambda: tmp_path_factory.mktemp("sharp"), (shape_key, wtype, name))
     return get
-
-
-class Worst:
-    """the largest max|gpu - f64| / max(1, std) of a test, and where"""
-
-    def __init__(self, what):
-        self.what, self.err, self.at = what, 0.0, None
-
-    def see(self, got, want64, at):
-        e = ac.rel_err(got, want64)
-        if e > self.err:
-            self.err, self.at = e, at
-        return e
-
-    def close(self, run=None):
-        note = ""
-        if run is not None and isinstance(self.at, int):
-            note = f", smallest top-two margin of that step {float(run.top2_gap[self.at].min()):.2f} nats"
-        print(f"\n{self.what}: max|gpu-f64|/max(1,std) = {self.err:.2e} (at {self.at}{note})")
-        assert self.err <= TOL, (self.what, self.err, self.at)
-
-
-def _kinds(dev, pos):
-    return {k: c for k, (ms, c) in dev.profile_forward(5, pos, iters=1).items() if c}
-
-
-def _teacher_forced(dev, toks, run, w):
-    for pos, t in enumerate(toks):
-        dev.forward(t, pos)
-        w.see(dev.state.logits, run.logits[pos], pos)
 
 
 # ---- 1. the general single-token plan: attn_kernel, its 128-key splits and the merge in the WO GEMV's prologue ------------------
@@ -146,60 +109,8 @@ def test_wide_tier_projection_attention_launch(hip, case, monkeypatch, name, wo)
 
 # ---- 4. the persistent decode: pd_decode_kernel through nl_decode_greedy and through the resident session -----------------------
 
-class _PlacementMiss(Exception):
-    pass
-
-
-def _no_warning(dev):
-    err = dev.last_error()
-    if "not placed 32 per XCD" in err:       # a property of the moment on the device (nl_persist.h): the chunk was redone on the
-        raise _PlacementMiss(err)            # launch plans, so the run did not test the persistent path
-    return err == ""
-
-
-def _persistent(hip, g, toks, f64, run, what):
-    dev = hip.load_llama_model(g)
-    try:
-        info = dev.persist_info()
-        assert info["ready"] and info["max_pos"] == 320, info
-        # (a) the resident session: per-call Forward over the whole sequence, passes of 128 keys from position 128 and 256 on
-        w = Worst(f"persistent decode, resident session {what}")
-        _teacher_forced(dev, toks, run, w)
-        info = dev.persist_info()          # (one resident launch unless the host paused longer than the idle limit)
-        assert _no_warning(dev) and info["tokens"] == len(toks) and 1 <= info["launches"] <= 4, info
-        # (b) chained greedy steps at positions 100 .. 159: below 128 a head's single record, above it the merge of the records
-        # in LDS.  The device picks its own tokens; the float64 forward is fed the ids it produced.
-        dev.reset()
-        n0, steps = ac.PERSIST_PROMPT, ac.PERSIST_STEPS
-        dev.prefill(toks[:n0])
-        tok = int(np.argmax(dev.state.logits))
-        fed, rows = [], []
-        for i in range(steps):
-            fed.append(tok)
-            (tok,) = dev.decode_greedy(tok, n0 + i, 1)
-            rows.append(dev.debug_read("logits", g.meta.vocab_size))
-        info2 = dev.persist_info()
-        assert _no_warning(dev) and info2["tokens"] - info["tokens"] == steps, (info, info2)
-    finally:
-        dev.close()
-    seq = list(toks[:n0]) + fed
-    want = f64.forward(seq)
-    # the inputs' condition on the sequence the device chose (test_attn_cases_cpu.py pins it on the oracle's own chain): the CPU
-    # oracle, teacher-forced with the device's ids, stays within REF_CAP of float64 there too
-    errs, oracle_ids = ac.oracle_errs(g, seq, want)
-    picked = fed[1:] + [tok]                                         # the id the device chose at positions n0 .. n0 + steps - 1
-    same = sum(picked[i] == oracle_ids[n0 + i] for i in range(steps))
-    print(f"\npersistent decode, greedy chain {what}: max|oracle-f64| on the device's ids = {max(errs):.2e}; "
-          f"{same} of {steps} device ids are the oracle's (all: the device followed the oracle's own chain)")
-    assert max(errs) <= ac.REF_CAP, max(errs)
-    wg = Worst(f"persistent decode, greedy chain {what}")
-    for i in range(steps):
-        wg.see(rows[i], want.logits[n0 + i], n0 + i)
-    if what.endswith("/self"):             # on the ids the device chose the newest key still wins every row
-        cov = ac.coverage(want, range(n0, n0 + steps))
-        assert cov["max_is_newest_key"] == cov["rows"], cov
-    w.close(run)
-    wg.close(want)
+_PlacementMiss, _no_warning = ac.PlacementMiss, ac.no_warning
+_persistent = ac.persistent_run
 
 
 @pytest.mark.parametrize("shape_key", ["mha4", "gqa"])        # the kv = 4 and the kv = 2 instantiation
@@ -216,16 +127,8 @@ def test_persistent_decode(hip, case, name, shape_key):
 
 # ---- 5. decode batches: attn_kernel with items, its FIN variant, attn_rope_prologue and battn_merge_kernel ----------------------------
 
-# Five streams at ragged positions, five steps each.  A step's attention grid has as many 128-key splits as its deepest row needs
-# (batched_step, nl_engine.hip), and the engine rotates q / k inside the attention launch (attn_rope_prologue, which also adds the
-# biases and stores the K / V rows) only while that is at most two and the Q|K|V GEMM is the plain one (Q8_0 / F16 files; a Q4_0
-# file's short steps go to dgemm_kernel, which rotates in its own epilogue):
-#   one_split     every position below 128: attn_kernel<FIN> writes the WO fragments itself, no merge launch;  NL_ROPE_IN_ATTN acts
-#   two_splits    positions 3 .. 204, two streams cross 128: items + battn_merge_kernel over two partials;      NL_ROPE_IN_ATTN acts
-#   three_splits  positions 3 .. 294, straddling 128 and 256: items + battn_merge_kernel over three partials; the knob is inert (the
-#                 brope_kv launch rotates whatever it says), both values run because the step graph is keyed on it
-BATCH_STARTS = {"one_split": [0, 3, 60, 100, 122], "two_splits": [3, 100, 124, 126, 200], "three_splits": [3, 125, 127, 254, 290]}
-BATCH_STEPS = 5
+# the layouts (five streams at ragged positions, five steps each) and what each of them reaches: attn_cases.BATCH_STARTS
+BATCH_STARTS, BATCH_STEPS = ac.BATCH_STARTS, ac.BATCH_STEPS
 _Q8_BATCH = [("gqa", "q8_0", c) for c in THREE] + [("gqa_bias", "q8_0", c) for c in SHIFT] + [("gqa_conj", "q8_0", "sharp")]
 
 
@@ -240,15 +143,7 @@ def test_decode_batches(hip, case, monkeypatch, layout, shape_key, wtype, name):
     assert layout == "one_split" or any(s < 128 <= s + BATCH_STEPS - 1 for s in start)
 
     def steps(dev):
-        for s in range(ns):
-            if start[s]:
-                dev.prefill(toks[:start[s]], stream=s, want_logits=False)
-        out = []
-        for k in range(BATCH_STEPS):
-            pos = [start[s] + k for s in range(ns)]
-            ids, lg = dev.forward_batch(list(range(ns)), [toks[p] for p in pos], pos, want_logits=True)
-            out.append(lg.copy())
-        return np.stack(out)
+        return ac.batch_run(dev, toks, start)
 
     outs = {}
     for knob in ("1", "0"):
@@ -280,26 +175,16 @@ def test_decode_batches(hip, case, monkeypatch, layout, shape_key, wtype, name):
                          [("gqa", "q4_0", "sharp")] + [("gqa", "f16", c) for c in THREE] + [("gqa_bias", "q8_0", c) for c in SHIFT])
 def test_prompts(hip, case, monkeypatch, shape_key, wtype, name):
     g, toks, _, run = case(shape_key, wtype, name)
-    m = g.meta
-    hd, S = m.head_dim, m.seq_len
-    nkv = m.num_layers * m.num_kv_heads * S * hd
     last, cache = {}, {}
     for kv16_min in (16, 1 << 30):                             # images built once per layer for every prefix / converted per chunk
         monkeypatch.setenv("NL_KV16_MIN_TOKENS", str(kv16_min))
         dev = hip.load_llama_model(g)
         w = Worst(f"prompt, images from {kv16_min} tokens {shape_key}/{wtype}/{name}")
-        for n in (130, 257, 300):                              # a prompt's logits are its last row's: three prefixes
-            dev.reset()
-            dev.prefill(toks[:n])
-            last[kv16_min, n] = dev.state.logits.copy()
-            w.see(last[kv16_min, n], run.logits[n - 1], n - 1)
-        kv_worst = 0.0
-        for which, want in (("k_cache", run.k), ("v_cache", run.v)):
-            got = dev.debug_read(which, nkv).reshape(m.num_layers, m.num_kv_heads, S, hd)[:, :, :300]
-            cache[kv16_min, which] = got
-            d = float((np.abs(got.astype(np.float64) - want) / (1.0 + np.abs(want))).max())
-            print(f"\n{which} {shape_key}/{wtype}/{name}, images from {kv16_min}: max|gpu-f64|/(1+|v|) = {d:.2e}")
-            kv_worst = max(kv_worst, d)
+        lg, kv, kv_worst = ac.prompt_run(dev, g, toks, run, w, f"{shape_key}/{wtype}/{name}, images from {kv16_min}")
+        for n in ac.PROMPT_PREFIXES:
+            last[kv16_min, n] = lg[n]
+        for which in ("k_cache", "v_cache"):
+            cache[kv16_min, which] = kv[which]
         dev.close()
         w.close(run)
         assert kv_worst <= KV_TOL, kv_worst
@@ -321,33 +206,7 @@ def test_prompts(hip, case, monkeypatch, shape_key, wtype, name):
 
 # ---- 7. mixed steps: attn_seg_kernel for the prompt chunk, the per-token route as the other ---------------------------------------
 
-def _mixed_steps(toks, chunk):
-    """a 200-token prompt (stream 2) beside two decode rows that stand at 130 and 260.  chunk 199: ONE step carries the whole
-    prompt -- a single segment of 199 rows (seven query tiles of 32, tiles that straddle key 128) and its final token as an output
-    row; chunk 64: the same prompt admitted as 64 / 64 / 64 / 7 rows (segments that start at a position > 0, a short last one)."""
-    steps, a, b = [], 130, 260
-    bounds = [(p0, min(p0 + chunk, 199)) for p0 in range(0, 199, chunk)]
-    for k, (p0, p1) in enumerate(bounds):
-        out = [(0, a + k), (1, b + k)] + ([(2, 199)] if p1 == 199 else [])      # the final prompt token joins as an output row
-        rows = out + [(2, p) for p in range(p0, p1)]
-        steps.append(([s for s, _ in rows], [toks[p] for _, p in rows], [p for _, p in rows], len(out)))
-    k = len(bounds)
-    steps.append(([0, 1, 2], [toks[a + k], toks[b + k], toks[200]], [a + k, b + k, 200], 3))   # a decode step over the chunk's K / V
-    return steps
-
-
-def _mixed_run(hip, g, toks, chunk, knob, monkeypatch):
-    """the steps of _mixed_steps on a fresh handle: (logits of the output rows per step, their positions)"""
-    monkeypatch.setenv("NL_MIXED_ATTN", knob)
-    dev = hip.load_llama_model(g, max_streams=3)
-    dev.prefill(toks[:130], stream=0, want_logits=False)
-    dev.prefill(toks[:260], stream=1, want_logits=False)
-    got = []
-    for streams, tk, pos, n_out in _mixed_steps(toks, chunk):
-        ids, lg = dev.forward_mixed(streams, tk, pos, n_out, want_logits=True)
-        got.append((lg.copy(), pos[:n_out]))
-    dev.close()
-    return got
+_mixed_steps, _mixed_run = ac.mixed_steps, ac.mixed_run
 
 
 @pytest.mark.parametrize("chunk", [199, 64])
